@@ -11,9 +11,13 @@ of the per-window result records).  Iteration body = bundlenet.py:193-278 (Bundl
 features / random-init lambda MLP.
 
 One "step" = one full coarse->fine solve (50 LM iterations) of the rank's windows with the inputs already resident in
-HBM.  value = windows * 50 * steps / time over all ranks.  The JSON line also carries (rank 0, N = 1 only)
+HBM.  value = windows * 50 * steps / time over all ranks; ms_per_step = the time of one timed step.  The line also carries
   roofline     : the fused assembly (gather) kernel, algorithmic bytes 4*N_l*(C*F + K + 1) per window-iteration vs the
-                 kernel time measured with HIP events inside the timed region (banet_profile_begin/_end), peak 8 TB/s;
+                 kernel time measured with HIP events inside the timed region (banet_profile_begin/_end), peak 8 TB/s.
+A plain run stops there: set up, W warm-up steps, K timed steps, the outputs if --dump-outputs DIR is given (the last timed
+step's result records and solver state as DIR/<name>.npy, float32; the inputs are seeded, identical from run to run), the
+line.  With --full it also measures (the --no-* switches leave parts out again; rank 0, N = 1 only unless noted)
+  exact SYRK   : the same K steps with the exact bf16x3 SYRK on every level (value_exact_syrk; every rank);
   sweep        : the other batch sizes north_star names (B = 1, 8, 256 two-frame) and cfg-3 = configs[2] (5-frame sliding
                  window, batch 32), each with its own value / ms_per_solve / roofline, measured in the same process;
   parity       : window 0 solved on the GPU with a [4]*5 schedule and compared, level by level, with the numpy oracle
@@ -22,7 +26,9 @@ HBM.  value = windows * 50 * steps / time over all ranks.  The JSON line also ca
                  tolerance, iteration counts must equal the schedule;
   cpu_baseline : BASELINE.md section 2's protocol on the host cores: the level-0..4 chain at one iteration per level
                  (window 0), 3 warm-ups + >= 10 timed repeats, median / p10 / p90, numpy port and float32 torch port
-                 (oracle/torch_port.py, all intra-op threads); cfg-1 (160x120, K = 32, 3 iterations) timed the same way.
+                 (oracle/torch_port.py, all intra-op threads); cfg-1 (160x120, K = 32, 3 iterations) timed the same way;
+  backward     : the dense training step (forward + fused backward) at the headline's shape and batch;
+  N > 1 ranks  : BASELINE's two 8-GPU configurations as the sweep, run by all ranks.
 
 `python bench.py --gpus N` without a torch.distributed environment launches its own N ranks (torch.distributed.run,
 127.0.0.1); under torchrun it is one rank of the job.  Rank 0 prints the one JSON line -- COMPACT (< 4 KB: the contract's
@@ -103,7 +109,9 @@ class Problem:
         st = self.ba.new_state(T=self.T0)
         st, counts = self.ba.solve(iters, st, level_events=level_events)
         rec = parallel.pack_results(st.R, st.T, st.Wc, counts)
-        return parallel.gather_results(rec, total_windows), st
+        full = parallel.gather_results(rec, total_windows)
+        self.last_step = (full, st, counts)         # what the caller of this step receives (--dump-outputs)
+        return full, st
 
     def convergence_check(self, st, dev):
         import torch
@@ -730,6 +738,26 @@ def emit(out):
     print(compact_record(out), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(prob, out_dir):
+    """--dump-outputs DIR: the arrays the timed path handed its caller in its LAST timed step, one float32 DIR/<name>.npy each --
+    the all-gathered result records [windows_total, 12 + K + levels] (R | T | W | iterations per level, banet_amd/parallel.py)
+    and this rank's solver state (R, T, W, lambda, the last update, the step ratio) with the per-level iteration counts."""
+    import numpy as np
+    import torch
+    full, st, counts = prob.last_step
+    arrays = {"records": full, "R": st.R, "T": st.T, "W": st.Wc, "lambda": st.lambda_out, "delta": st.delta, "ratio": st.ratio,
+              "iters_per_level": torch.stack(counts, dim=1)}
+    arrays = {k: np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the %d-byte dump limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` outside a torch.distributed environment: become the launcher of N ranks on this node."""
     import socket
@@ -744,7 +772,7 @@ def self_launch(args, argv):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -756,6 +784,11 @@ def main():
     ap.add_argument("--width", type=int, default=W)
     ap.add_argument("--basis", type=int, default=K, help="depth-basis coefficients K")
     ap.add_argument("--iters", type=int, default=ITERS[0], help="LM iterations per level")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the exact-SYRK rerun, the in-line oracle parity, the CPU "
+                    "baseline, the sweep of other batch sizes / configurations and the `backward` block (each still subject to the "
+                    "--no-* switches below); without it a run times the headline steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last timed step computed "
+                    "(result records and solver state) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true", help="skip the sub-records (B = 1 / 8 / 256, cfg-1, cfg-3, cfg-5 share)")
     ap.add_argument("--no-parity", action="store_true", help="skip the in-line oracle parity records")
@@ -764,7 +797,11 @@ def main():
     ap.add_argument("--reserved", type=int, default=0, help="development: banet_level_t.flags bits for every level (A/B switches)")
     ap.add_argument("--no-exact-syrk", action="store_true", help="skip the second timed run with the exact bf16x3 SYRK on every level")
     ap.add_argument("--no-backward", action="store_true", help="skip the `backward` block (the dense training step: forward + fused backward)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -813,11 +850,13 @@ def main():
     prob = Problem(B, args.frames, Hh, Ww, Kk, 1234 + rank, dev, args.reserved)
     rank_times = {}
     elapsed, prof, st = timed_run(prob, iters, args.steps, args.warmup, total_windows, fence, world, dev, rank_times)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(prob, args.dump_outputs)
     check = prob.convergence_check(st, dev)
     # the same K steps with the exact form of the depth-block SYRK on EVERY level (fp32 operands as three bf16 pieces, six products:
     # fp32-exact like the reference's sgemm) -- `value` is measured with the scaled fp16 two-piece form on the large levels
     exact = None
-    if not args.no_exact_syrk and Kk in (64, 128, 256):
+    if args.full and not args.no_exact_syrk and Kk in (64, 128, 256):
         from banet_amd import ops as _ops
         lm_keep = getattr(prob, "level_ms", None)
         prob.set_flags(args.reserved | _ops.NO_SYRK_F16)
@@ -883,7 +922,7 @@ def main():
         out.update(rank_times)
         out["build_mode"] = os.environ.get("BANET_BUILD_MODE", _build_mode())
         if world == 1:
-            if headline and not args.no_parity:
+            if headline and args.full and not args.no_parity:
                 parity, base = parity_and_cpu_baseline(prob, dev, not args.no_cpu_baseline)
                 out["parity"] = parity
                 if base is not None:
@@ -891,7 +930,7 @@ def main():
             del prob, st
             gc.collect()
             torch.cuda.empty_cache()
-            if headline and not args.no_sweep:
+            if headline and args.full and not args.no_sweep:
                 sweep = {}
                 par = not args.no_parity
                 #            name                frames B   H    W     K   iters steps warm scales
@@ -908,12 +947,12 @@ def main():
                 out["co_headline"] = {"cfg3_5frame_B32": {k: sweep["cfg3_5frame_B32"][k] for k in ("value", "unit", "ms_per_step", "steps")},
                                       "note": "configs[2] is the only configuration BASELINE.json quotes literally at batch 32 on one "
                                               "MI355X; reported beside the 2-frame headline"}
-            if headline and not args.no_backward:
+            if headline and args.full and not args.no_backward:
                 out["backward"] = backward_record(dev, args.reserved)
     # ---- N ranks: BASELINE's two 8-GPU configurations, run by ALL ranks (configs[3]: 5-frame windows, 32 per GPU = batch 256 over
     # 8 GPUs; configs[4]: 8-frame 1280x960 K = 256 windows, 15 LM iterations per level, 8 per GPU = batch 64 over 8 GPUs), each
     # ending in the one all-gather of the solve records like the headline
-    if world > 1 and headline and not args.no_sweep:
+    if world > 1 and headline and args.full and not args.no_sweep:
         del prob, st
         gc.collect()
         torch.cuda.empty_cache()

@@ -14,7 +14,7 @@ done
 python tools/make_pmc_traffic.py /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE 32 $OUT/pmc_traffic.json | cut -c1-200
 cp $OUT/pmc_traffic.json profiles/pmc_traffic.json
 for bits in 0 536870912; do
-  timeout 300 python bench.py --gpus 1 --steps 10 --warmup 3 --no-sweep --no-cpu-baseline --reserved $bits > $OUT/bench_r$bits.log 2>/dev/null
+  timeout 300 python bench.py --full --gpus 1 --steps 10 --warmup 3 --no-sweep --no-cpu-baseline --reserved $bits > $OUT/bench_r$bits.log 2>/dev/null
   python - <<PY
 import json
 l=[x for x in open("$OUT/bench_r$bits.log") if x.startswith("{")]

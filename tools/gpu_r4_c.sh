@@ -26,7 +26,7 @@ print(sys.argv[2], d["value"], d["ms_per_step"], "frac", r["frac"], "gather", r[
 PY
 }
 for bits in 0 -2147483648 1073741824; do
-  timeout 900 python bench.py --steps 6 --warmup 2 --no-sweep --no-cpu-baseline --reserved=$bits > $OUT/c_bench_32_$bits.log 2>&1
+  timeout 900 python bench.py --full --steps 6 --warmup 2 --no-sweep --no-cpu-baseline --reserved=$bits > $OUT/c_bench_32_$bits.log 2>&1
   show $OUT/c_bench_32_$bits.log "B32 bits $bits"
 done
 for B in 1 8; do

@@ -18,7 +18,7 @@ print(sys.argv[2], d["value"], d["ms_per_step"], "frac", r["frac"], "gather", r[
 PY
 }
 for bits in 0 -2147483648 1073741824 -1073741824 0; do
-  timeout 900 python bench.py --steps 8 --warmup 3 --no-sweep --no-cpu-baseline --reserved=$bits > $OUT/d_bench_32_$bits.log 2> $OUT/d_bench_32_$bits.err
+  timeout 900 python bench.py --full --steps 8 --warmup 3 --no-sweep --no-cpu-baseline --reserved=$bits > $OUT/d_bench_32_$bits.log 2> $OUT/d_bench_32_$bits.err
   show $OUT/d_bench_32_$bits.log "B32 bits $bits"
   tail -2 $OUT/d_bench_32_$bits.err | cut -c1-300
 done

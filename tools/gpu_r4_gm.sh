@@ -19,8 +19,8 @@ print(sys.argv[2], d["build_id"], d["value"], d["ms_per_step"], "syrk", r["syrk_
 PY
 }
 for rep in 1 2; do
-  timeout 600 python bench.py --steps 8 --warmup 3 --no-sweep --no-cpu-baseline > $OUT/gm_base_$rep.log 2>&1; show $OUT/gm_base_$rep.log "headline in-tree"
-  BANET_HIP_LIB=$GM timeout 600 python bench.py --steps 8 --warmup 3 --no-sweep --no-cpu-baseline > $OUT/gm_new_$rep.log 2>&1; show $OUT/gm_new_$rep.log "headline gather-maxima"
+  timeout 600 python bench.py --full --steps 8 --warmup 3 --no-sweep --no-cpu-baseline > $OUT/gm_base_$rep.log 2>&1; show $OUT/gm_base_$rep.log "headline in-tree"
+  BANET_HIP_LIB=$GM timeout 600 python bench.py --full --steps 8 --warmup 3 --no-sweep --no-cpu-baseline > $OUT/gm_new_$rep.log 2>&1; show $OUT/gm_new_$rep.log "headline gather-maxima"
 done
 timeout 600 python bench.py --frames 5 --steps 3 --warmup 1 --no-sweep --no-cpu-baseline --no-parity > $OUT/gm_c3_base.log 2>&1; show $OUT/gm_c3_base.log "cfg3 in-tree"
 BANET_HIP_LIB=$GM timeout 600 python bench.py --frames 5 --steps 3 --warmup 1 --no-sweep --no-cpu-baseline --no-parity > $OUT/gm_c3_new.log 2>&1; show $OUT/gm_c3_new.log "cfg3 gather-maxima"

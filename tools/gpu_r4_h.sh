@@ -17,7 +17,7 @@ print(sys.argv[2], d["value"], d["ms_per_step"], "frac", r["frac"], "gather", r[
 PY
 }
 for bits in 0 -2147483648 0; do
-  timeout 900 python bench.py --steps 8 --warmup 3 --no-sweep --no-cpu-baseline --reserved=$bits > $OUT/h_bench_32_$bits.log 2> $OUT/h_bench_32_$bits.err
+  timeout 900 python bench.py --full --steps 8 --warmup 3 --no-sweep --no-cpu-baseline --reserved=$bits > $OUT/h_bench_32_$bits.log 2> $OUT/h_bench_32_$bits.err
   show $OUT/h_bench_32_$bits.log "B32 bits $bits"
 done
 python - <<'PY'

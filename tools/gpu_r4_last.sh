@@ -13,7 +13,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 { python tools/summarize_pmc.py /tmp/pmc_bwd_FETCH_SIZE; python tools/summarize_pmc.py /tmp/pmc_bwd_WRITE_SIZE; } > $OUT/last_pmc_backward_fetch_write.txt 2>&1
 head -30 $OUT/last_pmc_backward_fetch_write.txt | cut -c1-200
-( time timeout 1500 python bench.py ) > $OUT/last_bench_default.log 2> $OUT/last_bench_default.err; echo "bench exit $?" >> $OUT/last_bench_default.err
+( time timeout 1500 python bench.py --full ) > $OUT/last_bench_default.log 2> $OUT/last_bench_default.err; echo "bench exit $?" >> $OUT/last_bench_default.err
 tail -4 $OUT/last_bench_default.err
 python - <<'PY'
 import json

@@ -35,11 +35,11 @@ cp profiles/pmc_traffic.json $OUT/pmc_traffic.json
 rm -rf /tmp/prof && mkdir -p /tmp/prof
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o fin -- python $REPO/bench.py --gpus 1 --steps 4 --warmup 1 --no-cpu-baseline --no-parity --no-sweep --no-exact-syrk --no-backward > $REPO/$OUT/prof_run.log 2>&1)
 for f in $(find /tmp/prof -name "*kernel_stats.csv"); do cp "$f" $OUT/bench_kernel_stats_build_$BID.csv; done
-( time timeout 1800 python bench.py ) > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench exit $?" >> $OUT/bench_default.err
+( time timeout 1800 python bench.py --full ) > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench exit $?" >> $OUT/bench_default.err
 tail -4 $OUT/bench_default.err
 cp bench_detail.json $OUT/bench_detail.json 2>/dev/null
 grep '^{"metric"' $OUT/bench_default.log | tail -1 > $OUT/bench_default_line.json
-( BANET_BENCH_DEVICE=0 BANET_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 ) > $OUT/bench_2rank.log 2> $OUT/bench_2rank.err; echo "2rank exit $?" >> $OUT/bench_2rank.err
+( BANET_BENCH_DEVICE=0 BANET_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --steps 3 --warmup 1 ) > $OUT/bench_2rank.log 2> $OUT/bench_2rank.err; echo "2rank exit $?" >> $OUT/bench_2rank.err
 grep '^{"metric"' $OUT/bench_2rank.log | tail -1 > $OUT/bench_2rank_gloo_one_gpu_line.json
 tail -1 $OUT/bench_2rank.err
 # ---- the dense training step

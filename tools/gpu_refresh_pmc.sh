@@ -12,7 +12,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
   echo "$c exit $?"
 done
 python tools/make_pmc_traffic.py /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE 32 $OUT/pmc_traffic.json | cut -c1-400
-timeout 300 python bench.py --gpus 1 --steps 5 --warmup 2 --no-sweep --no-cpu-baseline 2>/dev/null | python -c "
+timeout 300 python bench.py --full --gpus 1 --steps 5 --warmup 2 --no-sweep --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -16,13 +16,13 @@ if [[ $MODE == tests || $MODE == all ]]; then
   tail -3 $OUT/smoke.log
 fi
 if [[ $MODE == bench || $MODE == all ]]; then
-  timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 > $OUT/bench.log 2>&1; echo "bench exit $?" >> $OUT/bench.log
+  timeout 900 python bench.py --full --gpus 1 --steps 5 --warmup 2 > $OUT/bench.log 2>&1; echo "bench exit $?" >> $OUT/bench.log
   tail -5 $OUT/bench.log
 fi
 if [[ $MODE == prof || $MODE == all ]]; then
   rm -rf /tmp/prof && mkdir -p /tmp/prof $OUT/prof
   REPO=$PWD
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r01 -- python $REPO/bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $REPO/$OUT/prof_run.log 2>&1)
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o r01 -- python $REPO/bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline > $REPO/$OUT/prof_run.log 2>&1)
   echo "prof exit $?" >> $OUT/prof_run.log
   tail -3 $OUT/prof_run.log
   find /tmp/prof -type f | head -20
@@ -33,7 +33,7 @@ if [[ $MODE == pmc || $MODE == all ]]; then
   rm -rf /tmp/pmc && mkdir -p /tmp/pmc
   REPO=$PWD
   for CNT in FETCH_SIZE WRITE_SIZE; do
-    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d /tmp/pmc -o $CNT -- python $REPO/bench.py --gpus 1 --steps 1 --warmup 0 --no-cpu-baseline > $REPO/$OUT/pmc_run_$CNT.log 2>&1)
+    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d /tmp/pmc -o $CNT -- python $REPO/bench.py --full --gpus 1 --steps 1 --warmup 0 --no-cpu-baseline > $REPO/$OUT/pmc_run_$CNT.log 2>&1)
     echo "pmc $CNT exit $?" >> $OUT/pmc_run_$CNT.log
     tail -2 $OUT/pmc_run_$CNT.log
   done

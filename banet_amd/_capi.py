@@ -68,6 +68,10 @@ EXPORTS = {
     "banet_resample_f32": (ctypes.c_int, [_FP] * 3 + [ctypes.c_int] * 6 + [_FP]),
     "banet_target_map_f32": (ctypes.c_int, [_FP] * 2 + [ctypes.c_int] * 4 + [_FP]),
     "banet_depth_output_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 3 + [_FP]),
+    "banet_resample_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "banet_resample_grad_f32": (ctypes.c_int, [_FP] * 5 + [ctypes.c_int] * 7 + [_FP, ctypes.c_size_t, _FP]),
+    "banet_depth_output_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "banet_depth_output_grad_f32": (ctypes.c_int, [_FP] * 6 + [ctypes.c_int] * 4 + [_FP, ctypes.c_size_t, _FP]),
     "banet_sample_stats_blocks": (ctypes.c_int, [ctypes.c_int]),
     "banet_sample_stats_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 5 + [_FP] * 3),
     "banet_sample_stats_grad_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 5 + [_FP] * 6),

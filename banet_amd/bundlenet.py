@@ -218,7 +218,9 @@ class BundleNet:
     as (filters [Cin,Cout], biases [Cout]) pairs -- the reference's TF variables
     `lambda_<level>_<i>_filters/_biases`."""
 
-    def __init__(self, is_training=True, reuse_variables=None, lambda_weights=None):
+    def __init__(self, is_training=True, reuse_variables=None, lambda_weights=None, prep_graph="torch"):
+        if prep_graph not in ("torch", "hip"):
+            raise ValueError("prep_graph must be 'torch' or 'hip', got %r" % (prep_graph,))
         self.is_training = is_training
         self.reuse_variables = reuse_variables
         self.lambda_weights = dict(lambda_weights or {})
@@ -233,11 +235,18 @@ class BundleNet:
         # adjoint, normal equations by block in torch (no samp / diff / grad / J tensors); both always exact gradients;
         # "reference" = the reference's statements one by one with the EquationConstruction op and its registered gradient
         self.training_graph = "fused"
+        # the level drivers' preparation when a gradient is needed (resampler, [f|gx|gy] target map, output depth): "torch" = the
+        # differentiable torch expressions (_resampler_autograd, _grad_fixed_autograd, a matmul); "hip" = torch.ops.banet.* of
+        # banet_amd/prep_grad.py, whose backwards are HIP kernels without float atomics (bit-reproducible, and they run under
+        # torch.use_deterministic_algorithms(True)).  Forward-only calls take the HIP kernels either way.
+        self.prep_graph = prep_graph
 
     # -- small helpers kept for API parity --------------------------------------------
     def grad_fixed(self, input, name=None):
         """bundlenet.py:92-100"""
         if _wants_grad(input):
+            if self.prep_graph == "hip":
+                return self._target_map(input)[..., input.shape[-1]:]     # backward: the target-map adjoint with a zero f part
             return _grad_fixed_autograd(input)
         C = input.shape[-1]
         return ops.target_map(input)[..., C:]          # [gx | gy] of ba_target_map_kernel
@@ -249,6 +258,24 @@ class BundleNet:
         w, b = self.lambda_weights[level][int(i) - 1]
         assert w.shape[-1] == num_out_layers
         return activation(torch.matmul(x, w.to(x.device)) + b.to(x.device))
+
+    def _resample(self, data, warp):
+        if self.prep_graph == "hip" and _wants_grad(data, warp):
+            from . import prep_grad
+            return prep_grad.resampler(data, warp)
+        return resampler(data, warp)
+
+    def _target_map(self, img):
+        if self.prep_graph == "hip" and _wants_grad(img):
+            from . import prep_grad
+            return prep_grad.target_map(img)
+        return _target_map(img)
+
+    def _depth_output(self, init_depth, basis, W):
+        if self.prep_graph == "hip" and _wants_grad(init_depth, basis, W):
+            from . import prep_grad
+            return prep_grad.depth_output(init_depth, basis, W)
+        return _depth_output(init_depth, basis, W)
 
     def computeCoordinates(self, points2d, fx, fy, ox, oy):
         """bundlenet.py:112-120 -> p [B,3,N] (unit rays)"""
@@ -456,7 +483,7 @@ class BundleNet:
         """bundlenet.py:280-329: 4 levels (scale 8,4,2,1) x 1 CameraIteration."""
         self.reuse_variables = reuse_variables
         _points = self._crop(points)
-        d = resampler(_depths.detach(), _points / 2)
+        d = self._resample(_depths.detach(), _points / 2)
         nbatch, npixels = layers[-1].shape[0], points.shape[1]
         self._crop_intrinsics(intrisic, npixels)
         p = self.computeCoordinates(_points, self.fx, self.fy, self.ox, self.oy)
@@ -465,8 +492,8 @@ class BundleNet:
         rotations, translations = [], []
         for level in range(0, 4):
             scale = 2 ** (3 - level)
-            layer1 = resampler(layers[level], _points / scale)
-            layer2 = _target_map(self._swap_halves(layers[level]))         # [f | gx | gy], differentiable when needed
+            layer1 = self._resample(layers[level], _points / scale)
+            layer2 = self._target_map(self._swap_halves(layers[level]))    # [f | gx | gy], differentiable when needed
             R, T = self.CameraIteration(layer1, layer2, self.fx / scale, self.fy / scale, self.ox / scale,
                                         self.oy / scale, p, d, R, T, 1.0, str(level))
             rotations.append(R)
@@ -479,8 +506,8 @@ class BundleNet:
         self.reuse_variables = reuse_variables
         _points = self._crop(points)
         depths = init_depth.detach()
-        d = resampler(depths, _points / 2)
-        b = resampler(basis, _points / 2)
+        d = self._resample(depths, _points / 2)
+        b = self._resample(basis, _points / 2)
         nbatch, npixels, nbasis = layers[-1].shape[0], points.shape[1], basis.shape[-1]
         self._crop_intrinsics(intrisic, npixels)
         p = self.computeCoordinates(_points, self.fx, self.fy, self.ox, self.oy)
@@ -492,13 +519,13 @@ class BundleNet:
         Hh, Wh = init_depth.shape[1], init_depth.shape[2]
         for level in range(2, 4):
             scale = 2 ** (3 - level)
-            layer1 = resampler(layers[level], _points / scale)
-            layer2 = _target_map(self._swap_halves(layers[level]))         # [f | gx | gy], differentiable when needed
+            layer1 = self._resample(layers[level], _points / scale)
+            layer2 = self._target_map(self._swap_halves(layers[level]))    # [f | gx | gy], differentiable when needed
             R, T, W = self.BundleIteration(layer1, layer2, self.fx / scale, self.fy / scale, self.ox / scale,
                                            self.oy / scale, p, d, b, R, T, W, 1000.0, str(level))
             out_R.append(R)
             out_T.append(T)
-            out_D.append(_depth_output(init_depth, basis, W))              # :397, differentiable w.r.t. init_depth / basis / W
+            out_D.append(self._depth_output(init_depth, basis, W))         # :397, differentiable w.r.t. init_depth / basis / W
         return out_R, out_T, out_D
 
     # -- losses (bundlenet.py:401-463) ---------------------------------------------------

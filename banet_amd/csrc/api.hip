@@ -336,6 +336,40 @@ int banet_depth_output_f32(const float* init_depth, const float* basis, const fl
   return launch_depth_output(init_depth, basis, Wc, out, B, N, K, static_cast<hipStream_t>(stream));
 }
 
+size_t banet_resample_grad_workspace_bytes(int B, int N, int C, int H, int W, int mode) {
+  if (B <= 0 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (mode != BANET_RESAMPLE_ZERO_PAD && mode != BANET_RESAMPLE_CLAMP)) return 0;
+  if (!resample_grad_supported(B, N, C, H, W)) return 0;
+  return resample_grad_workspace_bytes(B, N, C, H, W);
+}
+
+int banet_resample_grad_f32(const float* data, const float* warp, const float* gout, float* ddata, float* dwarp, int B, int N, int C,
+                            int H, int W, int mode, int flags, void* ws, size_t ws_bytes, banet_stream_t stream) {
+  if (!data || !warp || !gout) return BANET_ERR_INVALID_ARG;
+  if (B <= 0 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (mode != BANET_RESAMPLE_ZERO_PAD && mode != BANET_RESAMPLE_CLAMP))
+    return BANET_ERR_INVALID_ARG;
+  if (flags & ~BANET_ADJOINT_OVERWRITE) return BANET_ERR_INVALID_ARG;
+  if (!resample_grad_supported(B, N, C, H, W)) return BANET_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < resample_grad_workspace_bytes(B, N, C, H, W) || (reinterpret_cast<uintptr_t>(ws) & 255) != 0)
+    return BANET_ERR_WORKSPACE;
+  return launch_resample_grad(data, warp, gout, ddata, dwarp, B, N, C, H, W, mode, flags & BANET_ADJOINT_OVERWRITE, ws,
+                              static_cast<hipStream_t>(stream));
+}
+
+size_t banet_depth_output_grad_workspace_bytes(int B, int N, int K) {
+  if (B <= 0 || N <= 0 || K <= 0) return 0;
+  return depth_output_grad_workspace_bytes(B, N, K);
+}
+
+int banet_depth_output_grad_f32(const float* basis, const float* Wc, const float* gout, float* dinit, float* dbasis, float* dWc, int B,
+                                int N, int K, int flags, void* ws, size_t ws_bytes, banet_stream_t stream) {
+  if (!basis || !Wc || !gout) return BANET_ERR_INVALID_ARG;
+  if (B <= 0 || N <= 0 || K <= 0 || (flags & ~BANET_ADJOINT_OVERWRITE)) return BANET_ERR_INVALID_ARG;
+  if (!ws || ws_bytes < depth_output_grad_workspace_bytes(B, N, K) || (reinterpret_cast<uintptr_t>(ws) & 255) != 0)
+    return BANET_ERR_WORKSPACE;
+  return launch_depth_output_grad(basis, Wc, gout, dinit, dbasis, dWc, B, N, K, flags & BANET_ADJOINT_OVERWRITE, ws,
+                                  static_cast<hipStream_t>(stream));
+}
+
 int banet_sample_stats_blocks(int N) { return N > 0 ? sample_stats_blocks(N) : 0; }
 
 static bool sstats_shape_ok(int B, int N, int C, int H, int W) {

@@ -109,6 +109,15 @@ int launch_target_map(const float* img, float* out, int B, int H, int W, int C, 
 int launch_depth_output(const float* init, const float* basis, const float* Wc, float* out, int B, int N, int K,
                         hipStream_t s);
 
+// ---- prep_grad.hip ---------------------------------------------------------------------
+bool resample_grad_supported(int B, int N, int C, int H, int W);
+size_t resample_grad_workspace_bytes(int B, int N, int C, int H, int W);
+int launch_resample_grad(const float* data, const float* warp, const float* gout, float* ddata, float* dwarp, int B, int N, int C, int H,
+                         int W, int mode, int overwrite, void* ws, hipStream_t s);
+size_t depth_output_grad_workspace_bytes(int B, int N, int K);
+int launch_depth_output_grad(const float* basis, const float* Wc, const float* gout, float* dinit, float* dbasis, float* dWc, int B,
+                             int N, int K, int overwrite, void* ws, hipStream_t s);
+
 // ---- eqcon.hip -------------------------------------------------------------------------
 void launch_reduce(const float* partials, int B, int G, int pstride, int P, float* AtA, float* Atb, hipStream_t s);
 struct EqPlan {

@@ -280,6 +280,30 @@ int banet_target_map_f32(const float* img, float* out, int B, int H, int W, int 
 int banet_depth_output_f32(const float* init_depth, const float* basis, const float* Wc,
                            float* out, int B, int N, int K, banet_stream_t stream);
 
+/* (6b) gradients of the per-level preparation (what tf.gradients derives for bundlenet.py:320,343-344,385,397).
+ *   banet_resample_grad_f32   adjoint of banet_resample_f32 (same mode): given gout [B,N,C] = dL/dout,
+ *       ddata [B,H,W,C] = sum over the points' taps of tap weight x gout row (mode 0: taps outside the image and points
+ *            that are not sampled contribute nothing; mode 1: clamped taps on one texel each add their own weight);
+ *            summed per texel in ascending (point, tap) order with no float atomics: bit-reproducible;
+ *       dwarp [B,N,2] = sum_c gout . d out / d (x, y) with the forward's floor held fixed (the one-sided derivative at an
+ *            integer coordinate); 0 for a point mode 0 does not sample.  dwarp is always written.
+ *   banet_depth_output_grad_f32  adjoint of banet_depth_output_f32: dinit [B,N] = gout, dbasis [B,N,K] = gout Wc^T,
+ *       dWc [B,K] = sum_n gout basis (per-block partials in the workspace, folded in a fixed order).
+ *   Outputs may be NULL (not computed).  flags: BANET_ADJOINT_OVERWRITE (below) writes every entry of ddata / dinit / dbasis /
+ *   dWc, zeros where nothing lands; without it they are accumulated (+=).  Same bits as accumulating into zeros.
+ *   Limits (resampler): C <= 256 and B H W C < 2^32, else workspace_bytes = 0 and BANET_ERR_UNSUPPORTED.  The workspace
+ *   (256-byte aligned, at least workspace_bytes) is required.  Everything is enqueued on `stream` (graph-capturable).        */
+size_t banet_resample_grad_workspace_bytes(int B, int N, int C, int H, int W, int mode); /* 0 = unsupported */
+int banet_resample_grad_f32(const float* data, const float* warp, const float* gout,
+                            float* ddata /* [B,H,W,C] or NULL */, float* dwarp /* [B,N,2] or NULL */,
+                            int B, int N, int C, int H, int W, int mode, int flags,
+                            void* ws, size_t ws_bytes, banet_stream_t stream);
+size_t banet_depth_output_grad_workspace_bytes(int B, int N, int K);
+int banet_depth_output_grad_f32(const float* basis, const float* Wc, const float* gout,
+                                float* dinit, float* dbasis, float* dWc, /* each may be NULL */
+                                int B, int N, int K, int flags, void* ws, size_t ws_bytes,
+                                banet_stream_t stream);
+
 /* (7) differentiable layer support -- the C-wide part of one BundleIteration / CameraIteration in the reference's
  *     own tensor layout (bundlenet.py:230-243) and its adjoint (what TF autodiff derives from the same statements),
  *     so that a training graph never materialises samp [B,N,3C], diff, grad or J [B,N,2,P]:

@@ -8,7 +8,9 @@
 // upstream gradients of the updated state (gR', gT', gW'):
 //   small_pre_kernel    one workgroup per window: lambda MLP forward (activations kept), lambda; the adjoint of the SE(3) / W update
 //                       -> dL/d(R, T) (direct part) and dL/dsol; the damped matrix A and the right-hand side dL/dsol for the solve
-//   spd_solve_kernel    (solve.hip) lam_adj = A^-1 dL/dsol          [P < 32: a Cholesky in small_post_kernel instead]
+//   spd_solve_kernel    (solve.hip) lam_adj = A^-1 dL/dsol          [P < 32 -- bundle with 6 pairs + K < 32, i.e. K <= 25 on two-frame
+//                       windows, and camera windows of up to 5 target frames (P = 6 .. 30): a Cholesky in double on one thread of
+//                       small_post_kernel instead]
 //   small_post_kernel   one workgroup per window: dL/dAtb = lam_adj, dL/dA = -lam_adj sol^T (implicit function theorem, A = A^T),
 //                       dL/dAtA (diagonal x (1 + lambda) where damped), dL/dlambda -> dL/dy, dL/d||avg|| -> MLP backward (deltas
 //                       kept) -> dL/d avg -> dL/d sum|d|
@@ -235,42 +237,47 @@ __device__ void mlp_layer_backward(const float* __restrict__ Wt, int nin, int no
 __global__ __launch_bounds__(kSsThreads) void small_post_kernel(const SmallArgs a) {
   __shared__ float sG[2][1024];      // gradient w.r.t. a layer's output -> delta, ping-pong
   __shared__ float sRed[32];
-  __shared__ float sL[1024];         // P < 32: the matrix for the in-kernel Cholesky (P <= 31)
-  __shared__ float sX[64];
+  __shared__ double sL[31 * 31];     // P < 32: the matrix for the in-kernel Cholesky (P <= 31)
+  __shared__ double sX[32];
   const int b = blockIdx.x, tid = threadIdx.x, C = a.C, P = a.P, pairs = a.pairs;
   const float Nf = (float)a.N * (float)pairs;
   const float* __restrict__ sc = a.scal + (size_t)b * 4;
   const float lam = sc[0], nrm = sc[1], y = sc[2];
   const float* __restrict__ sol = a.delta + (size_t)b * P;
   float* __restrict__ ladj = a.ladj + (size_t)b * P;
-  if (P < 32) {     // pose only (P = 6): lam_adj = A^-1 dL/dsol by a Cholesky factorisation, one thread
+  if (P < 32) {     // below spd_solve_kernel's smallest size -- bundle with 6 pairs + K <= 31, camera windows of 1 .. 5 target frames:
+                    // lam_adj = A^-1 dL/dsol by an unpivoted Cholesky factorisation on one thread (A is the damped normal matrix:
+                    // positive definite; an A that float32 rounding made indefinite gives NaN, as the forward documents).  The
+                    // factor and both substitutions are kept in DOUBLE: in float32 the factorisation's own rounding was up to 5x
+                    // that of a float32 LU with partial pivoting once cond(A) reached ~1e4 (tests/test_gpu_small_step.py), and
+                    // <= 31^3 / 3 operations on one thread cost the same either way.
     const float* __restrict__ Ad = a.Ad + (size_t)b * P * P;
-    for (int e = tid; e < P * P; e += kSsThreads) sL[e] = Ad[e];
-    for (int i = tid; i < P; i += kSsThreads) sX[i] = a.rhs[(size_t)b * P + i];
+    for (int e = tid; e < P * P; e += kSsThreads) sL[e] = (double)Ad[e];
+    for (int i = tid; i < P; i += kSsThreads) sX[i] = (double)a.rhs[(size_t)b * P + i];
     __syncthreads();
     if (tid == 0) {
       for (int j = 0; j < P; ++j) {
-        float d = sL[j * P + j];
+        double d = sL[j * P + j];
         for (int k = 0; k < j; ++k) d -= sL[j * P + k] * sL[j * P + k];
-        d = sqrtf(d);
+        d = sqrt(d);
         sL[j * P + j] = d;
         for (int i = j + 1; i < P; ++i) {
-          float v = sL[i * P + j];
+          double v = sL[i * P + j];
           for (int k = 0; k < j; ++k) v -= sL[i * P + k] * sL[j * P + k];
           sL[i * P + j] = v / d;
         }
       }
       for (int i = 0; i < P; ++i) {
-        float v = sX[i];
+        double v = sX[i];
         for (int k = 0; k < i; ++k) v -= sL[i * P + k] * sX[k];
         sX[i] = v / sL[i * P + i];
       }
       for (int i = P - 1; i >= 0; --i) {
-        float v = sX[i];
+        double v = sX[i];
         for (int k = i + 1; k < P; ++k) v -= sL[k * P + i] * sX[k];
         sX[i] = v / sL[i * P + i];
       }
-      for (int i = 0; i < P; ++i) ladj[i] = sX[i];
+      for (int i = 0; i < P; ++i) ladj[i] = (float)sX[i];
     }
     __syncthreads();
   }

@@ -358,6 +358,7 @@ class _LevelSolve(torch.autograd.Function):
             sws = ops.ba_solve_update(prob, mlp, ba.l2_base, AtA, Atb, absres, nvalid, st, sws)
             saved.append((Ri, Ti, Wi, AtA, Atb, absres, st.delta.clone()))
         ctx.ba, ctx.li, ctx.saved = ba, li, saved
+        ctx.mlp = mlp                                  # THIS graph's lambda weights: solve_differentiable replaces ba.mlps[li] on every call
         ctx.layers = flat_layers
         ctx.shapes = (src.shape, tgt.shape, depth.shape, None if basis is None else basis.shape, R.shape, T.shape)
         return st.R.clone().reshape(R.shape), st.T.clone().reshape(T.shape), st.Wc.clone()
@@ -392,7 +393,7 @@ class _LevelSolve(torch.autograd.Function):
         if not ctx.saved:                                  # (no iteration ran: nothing writes the buffers)
             for t in [dsrc, ddepth, dbasis] + dmap3:
                 t.zero_()
-        hip_small = SmallStepHip(ba.variant, B, N, C, K, pairs, ba.mlps[li], ba.l2_base, dev) \
+        hip_small = SmallStepHip(ba.variant, B, N, C, K, pairs, ctx.mlp, ba.l2_base, dev) \
             if SmallStepHip.supported(ba.variant, B, N, C, K, pairs, dev) else None
         glayers = None if hip_small is not None else [torch.zeros_like(t) for t in flat]
         for Ri, Ti, Wi, AtA, Atb, absres, delta in reversed(ctx.saved):
@@ -540,7 +541,6 @@ class _SparseIteration(torch.autograd.Function):
         dT = dT.reshape(B, 3, 1) + dpose[:, 9:12].reshape(B, 3, 1)
         s1, s2, sD, sB, sR, sT, sW = ctx.shapes
         dWn = None if K == 0 else (dW.reshape(B, K, 1) + dpose[:, 12:].reshape(B, K, 1)).reshape(sW)
-        ctx.prob = ctx.inputs = None          # (release the aliased inputs now, not when the graph node dies)
         return (None, None, None, None, dsrc.reshape(s1), dmap3.reshape(s2), ddepth.reshape(sD), None if sB is None else dbasis.reshape(sB),
                 dR.reshape(sR), dT.reshape(sT), dWn, None, None, None, None, None) + glayers
 

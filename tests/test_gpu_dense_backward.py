@@ -181,8 +181,18 @@ def test_solve_differentiable_multi_frame_windows_match_oracle_finite_difference
     basis / W, P = 18 + K): forward values equal the fused window solve and the float64 oracle chain
     (banet_oracle.bundle_window_iteration), gradients w.r.t. the key-frame features, EVERY target frame, the depth, the basis
     and the lambda weights against central differences of that oracle chain."""
+    _multi_frame_windows_against_finite_differences(pairs=3, K=26)      # P = 44: the backward's solves run on banet_spd_solve_f32
+
+
+def test_solve_differentiable_multi_frame_windows_below_32_coefficients_match_oracle_finite_differences():
+    """The same check on a window with 2 target frames and K = 8: P = 20, the backward's solves run on the factorisation inside
+    small_post_kernel (csrc/smallstep.hip)."""
+    _multi_frame_windows_against_finite_differences(pairs=2, K=8)
+
+
+def _multi_frame_windows_against_finite_differences(pairs, K):
     from banet_amd import dense as bdense
-    H, W, C, K, B, pairs = 40, 48, 16, 26, 2, 3            # P = 44: the backward's solves run on banet_spd_solve_f32
+    H, W, C, B = 40, 48, 16, 2
     iters = [2, 1]
     scenes = [synth.make_window_scene(H, W, C, K, [2, 1], 61 + b, pairs, rot_mag=0.012, trans_mag=0.04) for b in range(B)]
     intr, levels = odense.batch_window_scene(scenes)

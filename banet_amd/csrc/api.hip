@@ -405,11 +405,11 @@ size_t banet_sample_stats_grad_workspace_bytes(int B, int N, int C, int H, int W
 int banet_sample_stats_grad_det_f32(const float* conv1, const float* conv2, const float* px, const float* py, int B, int N, int C,
                                     int H, int W, const float* dstats, const float* dabs, float* dconv1, float* dconv2,
                                     float* dpos, void* ws, size_t ws_bytes, banet_stream_t stream) {
-  if (!conv1 || !conv2 || !px || !py || !dstats || !dabs || !dconv1 || !dconv2 || !dpos || !ws) return BANET_ERR_INVALID_ARG;
+  if (!conv1 || !conv2 || !px || !py || !dstats || !dabs || !dconv1 || !dconv2 || !dpos) return BANET_ERR_INVALID_ARG;
   if (!sstats_shape_ok(B, N, C, H, W)) return BANET_ERR_INVALID_ARG;
   const size_t need = sample_stats_grad_det_workspace_bytes(B, N, C, H, W);
   if (need == 0) return BANET_ERR_UNSUPPORTED;
-  if (ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255) != 0) return BANET_ERR_WORKSPACE;
+  if (!ws || ws_bytes < need || !aligned256(ws)) return BANET_ERR_WORKSPACE;   // a missing workspace is a workspace error, as everywhere
   return launch_sample_stats_grad_det(conv1, conv2, px, py, B, N, C, H, W, dstats, dabs, dconv1, dconv2, dpos, ws,
                                       static_cast<hipStream_t>(stream));
 }
@@ -428,14 +428,14 @@ size_t banet_dense_adjoint_workspace_bytes_ex(const banet_level_t* lv, int flags
 int banet_dense_adjoint_ex_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const float* gAtA,
                                const float* gAtb, const float* gabs, float* dsrc, float* dmap3, float* ddepth, float* dbasis,
                                float* dpose, int flags, void* ws, size_t ws_bytes, banet_stream_t stream) {
-  if (!lv || !R || !T || !gAtA || !gAtb || !gabs || !dsrc || !dmap3 || !ddepth || !dpose || !ws) return BANET_ERR_INVALID_ARG;
+  if (!lv || !R || !T || !gAtA || !gAtb || !gabs || !dsrc || !dmap3 || !ddepth || !dpose) return BANET_ERR_INVALID_ARG;
   if (lv->K > 0 && (!Wc || !dbasis || !lv->basis)) return BANET_ERR_INVALID_ARG;     // K = 0 (pose only): no coefficient / basis tensors
   if (lv->B <= 0 || lv->N <= 0 || !lv->src || !lv->tgt || !lv->depth) return BANET_ERR_INVALID_ARG;
   if (lv->dense ? !lv->intr : (!lv->rays || !lv->fx || !lv->fy || !lv->ox || !lv->oy)) return BANET_ERR_INVALID_ARG;
   if (flags & ~(BANET_ADJOINT_OVERWRITE | BANET_ADJOINT_OVERWRITE_MAP | BANET_ADJOINT_FOLD_TARGET | BANET_ADJOINT_REUSE_DEPTH_SEED | BANET_ADJOINT_TILE_SHAPE(15))) return BANET_ERR_INVALID_ARG;
   const size_t need = dense_adjoint_workspace_bytes(lv, flags);
   if (need == 0) return BANET_ERR_UNSUPPORTED;
-  if (ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255) != 0) return BANET_ERR_WORKSPACE;
+  if (!ws || ws_bytes < need || !aligned256(ws)) return BANET_ERR_WORKSPACE;
   return launch_dense_adjoint(lv, R, T, Wc, gAtA, gAtb, gabs, dsrc, dmap3, ddepth, dbasis, dpose, flags, ws,
                               static_cast<hipStream_t>(stream));
 }
@@ -463,7 +463,7 @@ int banet_small_step_adjoint_f32(int variant, int B, int N, int C, int K, int pa
                                  const float* AtA, const float* Atb, const float* absres, const float* delta, const float* R,
                                  const float* T, const float* gR, const float* gT, const float* gW, float* gAtA, float* gAtb, float* gabs,
                                  float* dR, float* dT, const banet_mlp_t* gmlp, void* ws, size_t ws_bytes, banet_stream_t stream) {
-  if (!mlp || !gmlp || !AtA || !Atb || !absres || !delta || !R || !T || !gR || !gT || !gAtA || !gAtb || !gabs || !dR || !dT || !ws)
+  if (!mlp || !gmlp || !AtA || !Atb || !absres || !delta || !R || !T || !gR || !gT || !gAtA || !gAtb || !gabs || !dR || !dT)
     return BANET_ERR_INVALID_ARG;
   if (K > 0 && !gW) return BANET_ERR_INVALID_ARG;
   for (int i = 0; i < 5; ++i)
@@ -471,7 +471,7 @@ int banet_small_step_adjoint_f32(int variant, int B, int N, int C, int K, int pa
   if (B <= 0 || N <= 0 || C <= 0 || K < 0 || pairs < 1) return BANET_ERR_INVALID_ARG;
   const size_t need = small_step_workspace_bytes(variant, B, N, C, K, pairs);
   if (need == 0) return BANET_ERR_UNSUPPORTED;
-  if (ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255) != 0) return BANET_ERR_WORKSPACE;
+  if (!ws || ws_bytes < need || !aligned256(ws)) return BANET_ERR_WORKSPACE;
   return launch_small_step_adjoint(variant, B, N, C, K, pairs, l2_regularizer_base, mlp, AtA, Atb, absres, delta, R, T, gR, gT, gW, gAtA,
                                    gAtb, gabs, dR, dT, gmlp, ws, static_cast<hipStream_t>(stream));
 }

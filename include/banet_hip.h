@@ -11,6 +11,13 @@
  *   - asynchronous: work is enqueued on the caller's hipStream_t; nothing synchronises,
  *     allocates or frees; scratch comes from the caller-supplied workspace `ws`
  *     (size from the matching *_workspace_bytes query; 256-byte aligned);
+ *   - the workspace is pure scratch: on entry its contents are ARBITRARY (it need not be zeroed and
+ *     may hold another call's leftovers -- one arena can be recycled by calls of any shape); no call
+ *     reads a workspace byte it did not write itself, with one documented exception,
+ *     BANET_ADJOINT_REUSE_DEPTH_SEED, which reads what the previous banet_dense_adjoint_ex_f32 call
+ *     left; no call touches a byte outside [ws, ws + workspace_bytes); a NULL, misaligned or too
+ *     small `ws` is BANET_ERR_WORKSPACE wherever the query is non-zero (the one optional workspace,
+ *     banet_equation_construction_grad_f32's, selects the kernel that needs none instead);
  *   - stateless and re-entrant: no globals (the reference keeps per-GPU static scratch
  *     sized by the first call, utils.cu:214-216,259-264 -- not reproduced);
  *   - return value: BANET_OK or a negative BANET_ERR_* code; never throws.

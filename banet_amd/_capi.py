@@ -39,6 +39,44 @@ POLICY_THROUGHPUT, POLICY_BATCH_INVARIANT = 0, 1   # banet_hip.h: BANET_POLICY_*
 CANONICAL_BATCH = 32
 
 
+# banet_level_t.flags: every bit a source of the library consults, under the names of banet_amd/csrc/dev_flags.hpp (kDevFooBar ->
+# DEV_FOO_BAR; tests/test_plan_cpu.py compares the values).  0 in production.  As Level.flags
+# is an int32, bit 31 is the negative number.
+DEV_ABLATE_TAPS = 1 << 0           # every tap reads one fixed interior texel / point (generic kernel; BANET_ABLATE builds of the tile kernels)
+DEV_ABLATE_SOURCE_ROWS = 1 << 1    # patch kernel, BANET_ABLATE builds: every source row = pixels 0..3
+DEV_SPARSE_ITEMS64 = 1 << 1        # plan: sparse points stay 64 per wave item, never 16 (A/B; the bit's meaning outside BANET_ABLATE builds)
+DEV_ABLATE_DEPTH_DOT = 1 << 2      # no depth dot (generic kernel; BANET_ABLATE builds of the patch kernel)
+DEV_ABLATE_GATHER = 1 << 3         # no gather loop (generic kernel) / no tap arithmetic (BANET_ABLATE builds of the patch kernel)
+DEV_NO_QUARTER_TILES = 1 << 4      # direct tile kernel: never quarter-tile work items (A/B)
+DEV_GENERIC_GATHER = 1 << 5        # force the generic kernel where the C = 128 kernels would run (A/B experiments only)
+DEV_DIRECT_GATHER = 1 << 6         # the direct tile kernel instead of the patch kernel (A/B); also keeps the 4x4-item kernel off
+DEV_PATCH_NO_STAGING = 1 << 7      # patch kernel: no pixel group stages its bounding box in LDS (A/B)
+DEV_SYRK_NO_BF16X6 = 1 << 8        # SYRK: ba_syrk_direct_kernel (fp32 MFMA) / the LDS-tiled kernel instead of the bf16x6 / wide kernels (A/B)
+DEV_FORCE_PATCH_GATHER = 1 << 9    # the patch kernel at any size (parity tests)
+DEV_QUARTER_TILES = 1 << 10        # force quarter-tile work items (A/B); with kDevForceStripGather: 8-row strip segments (parity tests)
+DEV_PATCH_NO_STAGGER = 1 << 11     # patch kernel: the waves of a workgroup start together (A/B)
+DEV_PATCH_PAIR_LOOP = 1 << 12      # patch kernel: force the loop over a window's target frames inside a tile (parity tests)
+DEV_PATCH_ONE_PER_CU = 1 << 13     # patch kernel: 60 KB of unused dynamic LDS -> one workgroup per CU (A/B experiment, experiments/README.md)
+DEV_PATCH_UNITS4 = 1 << 14         # patch kernel: 4-step units (A/B, experiments/README.md)
+DEV_MLP_IN_SOLVE = 1 << 15         # LM loop: the lambda MLP inside the solve kernel, no role workgroups in the SYRK launch (A/B)
+DEV_PATCH_PACKED = 1 << 16         # patch kernel: the packed patch with flat loads (A/B)
+DEV_PATCH_COLUMN_MAJOR = 1 << 17   # patch kernel, 2-step units: column-major unit order (experiment)
+DEV_FORCE_STRIP_GATHER = 1 << 18   # the strip kernel at any size (parity tests)
+DEV_NO_STRIP_GATHER = 1 << 19      # never the strip kernel (A/B)
+DEV_STRIP_DIRECT_ROWS = 1 << 20    # strip kernel: every pixel row takes the direct (window-less) path (parity tests)
+DEV_STRIP_ROWS32 = 1 << 21         # strip kernel: 32-row segments (A/B, parity tests)
+DEV_STRIP_FRAME_LOOP = 1 << 22     # strip kernel: a window's frames looped over inside one wave, no frame-parallel workgroups (A/B)
+DEV_SOLVE_LDLT_ONLY = 1 << 23      # solve: blocked LDL^T only, no conjugate gradients (A/B and parity tests)
+DEV_SYRK_F16 = 1 << 24             # the fp16 two-piece SYRK also in a single assembly pass and at any launch size
+DEV_FORCE_QUAD_GATHER = 1 << 25    # the 4x4-pixel-item kernel at any size (parity tests, A/B)
+DEV_ADJ_FP32_MFMA = 1 << 26        # the fp32-MFMA kernel instead of the bf16x6 form of the GEMM-shaped piece (A/B)
+DEV_ADJ_PIXEL_PER_WAVE = 1 << 27   # one pixel per wave (A/B)
+DEV_ADJ_TEXEL_PER_WAVE = 1 << 28   # target-map kernel: one texel per wave (A/B)
+DEV_SYRK_THREE_PRODUCTS = 1 << 29  # opt-in, K = 128: the three largest of the six bf16 products only
+DEV_NO_QUAD_GATHER = 1 << 30       # never the 4x4-pixel-item kernel
+DEV_NO_SYRK_F16 = -(1 << 31)       # never the fp16 two-piece SYRK (A/B)
+
+
 class Mlp(ctypes.Structure):
     """mirror of banet_mlp_t"""
     _fields_ = [("w", _FP * 5), ("b", _FP * 5)]

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(kBlock, 2) void adj_basis_kernel(const AdjArgs a) {
 // The seed block is split ONCE per workgroup into LDS as MFMA B operands ([k step][column block][piece][lane], 3 KB per block and
 // k step: 108 KB at K = 128); a wave takes 16 pixels at a time: lane (m, kq) loads the 8 coefficients 32 ks + 8 kq .. + 7 of pixel
 // m (32 contiguous bytes; the four kq lanes of a pixel read 128), splits them (registers) and accumulates.  512 threads: two
-// waves per SIMD.  Epilogue as adj_basis_kernel (same accumulator layout).  flags bit 26 keeps the fp32-MFMA kernel (A/B).
+// waves per SIMD.  Epilogue as adj_basis_kernel (same accumulator layout).  kDevAdjFp32Mfma keeps the fp32-MFMA kernel (A/B).
 constexpr int kAdjB6Threads = 512, kAdjB6Waves = kAdjB6Threads / 64;
 // REUSE (BANET_ADJOINT_REUSE_DEPTH_SEED; the later target frames of a multi-frame window): S_dd, gAtb_d and the basis are those of the
 // previous call on this workspace, so z2 = 2 S_dd b, zeta and e are already there -- only the frame's own q = S_cd b is computed:
@@ -2271,7 +2271,7 @@ __global__ __launch_bounds__(kBlock) void sstats_rows_kernel(const float* __rest
 
 static void launch_adj_map(const AdjArgs& a, int C, dim3 grid, dim3 block, hipStream_t s) {
   const int C3 = 3 * C, J3 = (C3 + 63) / 64;
-  const bool half = (C3 & 3) == 0 && !(a.lv.flags & (1 << 28));   // bit 28: one texel per wave (A/B; bits 18 / 19 belong to the forward's gather selection)
+  const bool half = (C3 & 3) == 0 && !(a.lv.flags & kDevAdjTexelPerWave);   // one texel per wave (A/B)
   if (J3 <= 3) {
     if (half)
       hipLaunchKernelGGL((adj_map2_kernel<2, 3>), grid, block, 0, s, a);
@@ -2323,27 +2323,22 @@ void adj_plan(const banet_level_t* lv, int flags, AdjPlan* pl) {
   pl->Ga = (int)std::max<size_t>(1, std::min<size_t>((N + 63) / 64, (size_t)((512 + B - 1) / B)));
   pl->Gm = (int)std::max<size_t>(1, std::min<size_t>((HW + 3) / 4, (size_t)((4096 + B - 1) / B)));
   pl->bigq_cap = (int)(B * N / (kSortSerial + 1) + 1);               // every cell that could hold more than kSortSerial pixels
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  pl->off_S = take(B * P * P * 4);
-  pl->off_z2 = take(B * N * K * 4);
-  pl->off_arec = take(B * N * 8 * 4);
-  pl->off_arow = pl->fold ? 0 : take(B * N * 3 * C * 4);
-  pl->off_frac = take(B * N * kFrac * 4);
-  pl->off_cnt = take(B * HW * 4 + (pl->fold ? (size_t)(1 + pl->bigq_cap) * 4 : 0));   // fold: the big-cell queue follows, its counter zeroed with the counts
-  pl->off_start = take(B * HW * 8);
-  pl->off_cursor = take(B * HW * 4);
-  pl->off_list = take(B * N * 4);
-  pl->off_part = take(B * (size_t)pl->G * kNumWaves * (kAdjHdr + K) * 4);
-  pl->off_chunks = take(B * ((HW + 1023) / 1024) * 4);
-  pl->off_lrec = pl->fold ? take(B * N * kFrac * 4) : 0;
-  pl->off_list2 = pl->fold ? take(B * N * 4) : 0;
-  pl->off_lidx = pl->fold ? take(B * N * 8) : 0;
-  pl->bytes = o;
+  Arena ar;
+  pl->off_S = ar.take(B * P * P * 4);
+  pl->off_z2 = ar.take(B * N * K * 4);
+  pl->off_arec = ar.take(B * N * 8 * 4);
+  pl->off_arow = pl->fold ? 0 : ar.take(B * N * 3 * C * 4);
+  pl->off_frac = ar.take(B * N * kFrac * 4);
+  pl->off_cnt = ar.take(B * HW * 4 + (pl->fold ? (size_t)(1 + pl->bigq_cap) * 4 : 0));   // fold: the big-cell queue follows, its counter zeroed with the counts
+  pl->off_start = ar.take(B * HW * 8);
+  pl->off_cursor = ar.take(B * HW * 4);
+  pl->off_list = ar.take(B * N * 4);
+  pl->off_part = ar.take(B * (size_t)pl->G * kNumWaves * (kAdjHdr + K) * 4);
+  pl->off_chunks = ar.take(B * ((HW + 1023) / 1024) * 4);
+  pl->off_lrec = pl->fold ? ar.take(B * N * kFrac * 4) : 0;
+  pl->off_list2 = pl->fold ? ar.take(B * N * 4) : 0;
+  pl->off_lidx = pl->fold ? ar.take(B * N * 8) : 0;
+  pl->bytes = ar.off;
 }
 
 // ---- launch of the tile kernel: (channel chunks, vector width) by C; tile shape by flags bits 4-6 (A/B) ----
@@ -2491,7 +2486,7 @@ int launch_dense_adjoint(const banet_level_t* lv, const float* R, const float* T
   const size_t tot = (size_t)B * P * P;
   hipLaunchKernelGGL(adj_sym_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, gAtA, S, P, tot);
   if (hipMemsetAsync(a.cnt, 0, ((size_t)B * HW + (pl.fold ? 1 : 0)) * sizeof(int), s) != hipSuccess) return BANET_ERR_LAUNCH;
-  const bool b6 = !(lv->flags & (1 << 26));   // the bf16x6 form of the GEMM-shaped piece (bit 26: fp32 MFMA, A/B)
+  const bool b6 = !(lv->flags & kDevAdjFp32Mfma);   // the bf16x6 form of the GEMM-shaped piece (kDevAdjFp32Mfma: fp32 MFMA, A/B)
   a.reuse_z = ((flags & BANET_ADJOINT_REUSE_DEPTH_SEED) && b6 && K > 16 && K <= 128) ? 1 : 0;     // (the other forms recompute: same result)
   switch ((K + 15) / 16) {
     case 1: launch_adj_basis<1>(a, pl.Ga, s); break;
@@ -2530,7 +2525,7 @@ int launch_dense_adjoint(const banet_level_t* lv, const float* R, const float* T
     BANET_ADJ_POINT(1, 4);
     BANET_ADJ_POINT(2, 4);
 #undef BANET_ADJ_POINT
-  } else if ((lv->C & 3) == 0 && (K & 3) == 0 && lv->C <= 128 && K <= 128 && !(lv->flags & (1 << 27)) &&   // bit 27: one pixel per wave (A/B)
+  } else if ((lv->C & 3) == 0 && (K & 3) == 0 && lv->C <= 128 && K <= 128 && !(lv->flags & kDevAdjPixelPerWave) &&   // one pixel per wave (A/B)
              (size_t)N * 3 * lv->C < ((size_t)1 << 30) && N < (1 << 24)) {   // (32-bit byte offsets inside a window: its largest array is the N x 3C adjoint rows; 24-bit multiplies)
     if (a.overwrite)
       hipLaunchKernelGGL((adj_pixel2_kernel<1, true>), dim3(pl.G, B), dim3(kBlock), 0, s, a);   // (C = 256: 264 B of spills -> the one-pixel kernel)
@@ -2582,20 +2577,15 @@ struct DetPlan {
 };
 void det_plan(int B, int N, int C, int H, int W, DetPlan* pl) {
   const size_t HW = (size_t)H * W;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  pl->off_arow = take((size_t)B * N * 3 * C * 4);
-  pl->off_frac = take((size_t)B * N * kFrac * 4);
-  pl->off_cnt = take((size_t)B * HW * 4);
-  pl->off_start = take((size_t)B * HW * 8);
-  pl->off_cursor = take((size_t)B * HW * 4);
-  pl->off_list = take((size_t)B * N * 4);
-  pl->off_chunks = take((size_t)B * ((HW + 1023) / 1024) * 4);
-  pl->bytes = o;
+  Arena ar;
+  pl->off_arow = ar.take((size_t)B * N * 3 * C * 4);
+  pl->off_frac = ar.take((size_t)B * N * kFrac * 4);
+  pl->off_cnt = ar.take((size_t)B * HW * 4);
+  pl->off_start = ar.take((size_t)B * HW * 8);
+  pl->off_cursor = ar.take((size_t)B * HW * 4);
+  pl->off_list = ar.take((size_t)B * N * 4);
+  pl->off_chunks = ar.take((size_t)B * ((HW + 1023) / 1024) * 4);
+  pl->bytes = ar.off;
 }
 }  // namespace
 

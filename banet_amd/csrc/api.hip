@@ -36,11 +36,10 @@ struct LevelWs {  // carve of the level workspace
 static LevelWs carve_level(const banet_level_t* lv, const AsmPlan& pl, void* ws) {
   LevelWs w;
   char* p = static_cast<char*>(ws);
-  size_t off = 0;
+  Arena ar;
   auto take = [&](size_t bytes) {
-    char* r = p ? p + off : nullptr;
-    off += align_up(bytes, 256);
-    return r;
+    const size_t at = ar.take(bytes);
+    return p ? p + at : nullptr;   // (ws == nullptr: the size query)
   };
   w.partials = reinterpret_cast<float*>(take(pl.ws_bytes));
   w.AtA = reinterpret_cast<float*>(take((size_t)lv->B * pl.P * pl.P * sizeof(float)));
@@ -51,7 +50,7 @@ static LevelWs carve_level(const banet_level_t* lv, const AsmPlan& pl, void* ws)
   w.mlp_y = reinterpret_cast<float*>(take((size_t)lv->B * sizeof(float)));
   const size_t big = solve_big_bytes(lv->B, pl.P, lv->C);
   w.bigA = big ? reinterpret_cast<float*>(take(big)) : nullptr;
-  w.total = off;
+  w.total = ar.off;
   return w;
 }
 
@@ -151,7 +150,7 @@ int banet_equation_construction_grad_f32(const float* J, const float* G, const f
 
 size_t banet_ba_assemble_workspace_bytes(const banet_level_t* lv) {
   AsmPlan pl;
-  if (plan_assemble(lv, &pl) != BANET_OK) return 0;
+  if (plan_assemble(lv, num_cus(), &pl) != BANET_OK) return 0;
   return align_up(pl.ws_bytes, 256);
 }
 
@@ -161,7 +160,7 @@ int banet_ba_assemble_f32(const banet_level_t* lv, const float* R, const float* 
   if (rc != BANET_OK) return rc;
   if (!R || !T || !AtA || !Atb || !absres || !nvalid || (lv->K > 0 && !Wc)) return BANET_ERR_INVALID_ARG;
   AsmPlan pl;
-  rc = plan_assemble(lv, &pl);
+  rc = plan_assemble(lv, num_cus(), &pl);
   if (rc != BANET_OK) return rc;
   if (!ws || ws_bytes < pl.ws_bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
   return launch_assemble(lv, pl, R, T, Wc, nullptr, 0, ws, AtA, Atb, absres, nvalid,
@@ -175,7 +174,7 @@ int banet_ba_assemble_mask_f32(const banet_level_t* lv, const float* R, const fl
   if (rc != BANET_OK) return rc;
   if (!R || !T || !AtA || !Atb || !absres || !nvalid || !mask_out || (lv->K > 0 && !Wc)) return BANET_ERR_INVALID_ARG;
   AsmPlan pl;
-  rc = plan_assemble(lv, &pl);
+  rc = plan_assemble(lv, num_cus(), &pl);
   if (rc != BANET_OK) return rc;
   if (!ws || ws_bytes < pl.ws_bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
   return launch_assemble(lv, pl, R, T, Wc, nullptr, 0, ws, AtA, Atb, absres, nvalid, static_cast<hipStream_t>(stream), true,
@@ -220,7 +219,7 @@ int banet_ba_solve_update_ws_f32(const banet_level_t* lv, const banet_mlp_t* mlp
 
 size_t banet_lm_level_workspace_bytes(const banet_level_t* lv) {
   AsmPlan pl;
-  if (plan_assemble(lv, &pl) != BANET_OK) return 0;
+  if (plan_assemble(lv, num_cus(), &pl) != BANET_OK) return 0;
   return carve_level(lv, pl, nullptr).total;
 }
 
@@ -248,7 +247,7 @@ int banet_lm_level_ex_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float
   if (rc != BANET_OK) return rc;
   if (max_iters < 0) return BANET_ERR_INVALID_ARG;
   AsmPlan pl;
-  rc = plan_assemble(lv, &pl);
+  rc = plan_assemble(lv, num_cus(), &pl);
   if (rc != BANET_OK) return rc;
   if (!ws || !aligned256(ws)) return BANET_ERR_WORKSPACE;
   LevelWs w = carve_level(lv, pl, ws);
@@ -297,7 +296,7 @@ int banet_lm_level_ex_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float
     const bool role = lv->variant == BANET_BUNDLE && mlp != nullptr && a.use_mlp && syrk_runs_mlp_role(pl.s) && lv->C <= 256 &&
                       (lv->C & 3) == 0 && ((long long)Bsel * (pl.s.Gs + 1) <= num_cus() || (Bsel <= 8 && pl.s.Gs >= 16) ||
                        (lv->N <= kRoleSmallLevel && pl.s.Gs >= 4)) &&
-                      !(lv->flags & 32768);   // flags bit 15: MLP inside the solve kernel (A/B)
+                      !(lv->flags & kDevMlpInSolve);   // MLP inside the solve kernel (A/B)
     if (role) {
       a.mlp_y = w.mlp_y;
       if ((long long)Bsel * (pl.s.Gs + 1) > num_cus()) pl.s.Gs -= 1;
@@ -483,14 +482,14 @@ int banet_profile_ranges(int enable) { return profile_ranges(enable); }
 
 int banet_gather_selection(const banet_level_t* lv) {
   GatherPlan pl;
-  const int rc = plan_gather(lv, &pl);
+  const int rc = plan_gather(lv, num_cus(), &pl);
   if (rc != BANET_OK) return rc;
   return pl.quad ? 4 : pl.strip ? 3 : pl.patch ? 2 : pl.c128 ? 1 : 0;
 }
 
 int banet_syrk_selection(const banet_level_t* lv) {
   AsmPlan pl;
-  const int rc = plan_assemble(lv, &pl);
+  const int rc = plan_assemble(lv, num_cus(), &pl);
   if (rc != BANET_OK) return rc;
   if (lv->K == 0) return -1000;
   return pl.s.f16 ? 4 : pl.s.direct;

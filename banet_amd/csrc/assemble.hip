@@ -143,18 +143,6 @@ int num_cus() {
   return n;
 }
 
-int plan_assemble(const banet_level_t* lv, AsmPlan* pl) {
-  int rc = plan_gather(lv, &pl->g);
-  if (rc != BANET_OK) return rc;
-  rc = plan_syrk(lv->B, selection_batch(lv), lv->N, lv->K, npairs(lv), lv->flags, &pl->s);
-  if (rc != BANET_OK) return rc;
-  pl->P = 6 * npairs(lv) + lv->K;
-  pl->off_rec = pl->g.partial_bytes;
-  pl->off_spart = pl->off_rec + pl->g.rec_bytes;
-  pl->ws_bytes = pl->off_spart + pl->s.partial_bytes;
-  return BANET_OK;
-}
-
 int* assemble_queue(const AsmPlan& pl, void* ws) {
   return pl.g.c128 ? reinterpret_cast<int*>(static_cast<char*>(ws) + pl.g.off_queue) : nullptr;
 }

@@ -3,14 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/banet_hip.h"
+#include "plan.hpp"   // kWave / kBlock / kTilePix / kNumWaves, align_up, the launch plans (host-only)
 
 namespace banet {
-
-constexpr int kWave = 64;         // CDNA wavefront
-constexpr int kTilePix = 64;      // source pixels per workgroup tile (8x8 patch in dense mode)
-constexpr int kBlock = 256;       // 4 waves
-constexpr int kNumWaves = kBlock / kWave;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -114,7 +109,5 @@ __device__ __forceinline__ Q5 q5_finish(Q5 q) {  // remaining lane bits 1,0
 // (bundlenet.py:97-99): at the border both neighbours coincide -> zero gradient.
 __device__ __forceinline__ int refl_m(int i) { return i == 0 ? 1 : i - 1; }
 __device__ __forceinline__ int refl_p(int i, int n) { return i == n - 1 ? n - 2 : i + 1; }
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace banet

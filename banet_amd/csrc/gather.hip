@@ -11,7 +11,7 @@
 //   record (u = Jc^T M jd, s = jd^T M jd, r = jd^T g) for the depth-basis blocks (syrk.hip)
 //
 // This file: the GENERIC kernel (any C <= 256, K <= 256, sparse points, the reference's precomputed [f|gx|gy]
-// target layout) plus the planning / dispatch of all gather kernels; the C = 128 dense fast paths live in
+// target layout) plus the dispatch of all gather kernels (their planning: plan.hpp); the C = 128 dense fast paths live in
 // gather128.hip (direct loads) and gather128p.hip (wave-private LDS patches, large levels).
 // Design: NO workgroup barriers and no LDS in the main loop -- every wave is an independent
 // stream, so occupancy (3 waves/SIMD) hides the dependent chain basis-row -> depth -> projection
@@ -27,10 +27,6 @@
 //   4. 6x6 algebra with lane = pixel; H_cc in LDS accumulators (one owner per address, plain read-modify-write).
 #include <algorithm>
 #include "gather_common.hpp"
-
-#ifndef BANET_GATHER_WAVES
-#define BANET_GATHER_WAVES 3
-#endif
 
 namespace banet {
 
@@ -120,7 +116,7 @@ __global__ __launch_bounds__(kBlock, BANET_GATHER_WAVES) void ba_gather_kernel(c
     float D = valid ? dep_b[pt] : 0.f;
     if constexpr (KCH > 0) {
       float pend[6], dsum = 0.f;
-      for (int q8 = 0; q8 < ((dbg & 4) ? 0 : 8); ++q8) {
+      for (int q8 = 0; q8 < ((dbg & kDevAblateDepthDot) ? 0 : 8); ++q8) {
         float part[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -227,7 +223,7 @@ __global__ __launch_bounds__(kBlock, BANET_GATHER_WAVES) void ba_gather_kernel(c
       // on-the-fly gradient go to the slow path and look masked to the main loop
       const bool interior = (x0 >= 1) && (x0 + 2 <= W - 1) && (y0 >= 1) && (y0 + 2 <= H - 1);
       const bool fast = m && (GRAD || interior);
-      gflags = (m ? 1 : 0) | (fast ? 2 : 0) | ((m && !fast) ? 4 : 0);
+      gflags = (m ? kPixInMask : 0) | (fast ? kPixFast : 0) | ((m && !fast) ? kPixRim : 0);
       gx0 = x0;
       gy0 = y0;
       sx0 = fast ? x0 : 1;
@@ -238,7 +234,7 @@ __global__ __launch_bounds__(kBlock, BANET_GATHER_WAVES) void ba_gather_kernel(c
     // ---- 3. gather: pixel j's scalars from lane j, rows as coalesced 512-B loads -----------
     auto pixel_q5 = [&](int j) __attribute__((always_inline)) -> Q5 {
       Q5 q{0.f, 0.f, 0.f, 0.f, 0.f};
-      const int x0 = (dbg & 1) ? 1 : rdl(sx0, j), y0 = (dbg & 1) ? 1 : rdl(sy0, j);  // safe interior texel when not on the fast path
+      const int x0 = (dbg & kDevAblateTaps) ? 1 : rdl(sx0, j), y0 = (dbg & kDevAblateTaps) ? 1 : rdl(sy0, j);  // safe interior texel when not on the fast path
       const float mk = rdl(smk, j);
       const float w00 = mk * rdl(gw00, j), w01 = mk * rdl(gw01, j), w10 = mk * rdl(gw10, j), w11 = mk * rdl(gw11, j);
       const int ptj = rdl(pt, j);
@@ -303,7 +299,7 @@ __global__ __launch_bounds__(kBlock, BANET_GATHER_WAVES) void ba_gather_kernel(c
     Q5 q{0.f, 0.f, 0.f, 0.f, 0.f};
     {
       Q5 pend[6];
-      for (int tt = 0; tt < ((dbg & 8) ? 0 : 64); tt += 2) {
+      for (int tt = 0; tt < ((dbg & kDevAblateGather) ? 0 : 64); tt += 2) {
         const int j0 = brev6(tt);          // leaf tt+1 is pixel j0 + 32
         BANET_TICK(t0);
         const Q5 zero5{0.f, 0.f, 0.f, 0.f, 0.f};
@@ -339,7 +335,7 @@ __global__ __launch_bounds__(kBlock, BANET_GATHER_WAVES) void ba_gather_kernel(c
     }
     if constexpr (!GRAD) {
       // patch the pixels whose stencil touches the image rim (rare)
-      unsigned long long slow = __ballot((gflags & 4) != 0);
+      unsigned long long slow = __ballot((gflags & kPixRim) != 0);
       while (slow) {  // wave-uniform
         const int j = __builtin_ctzll(slow);
         slow &= slow - 1;
@@ -378,8 +374,8 @@ __global__ __launch_bounds__(kBlock, BANET_GATHER_WAVES) void ba_gather_kernel(c
         }
 #pragma unroll
       for (int i = 0; i < 6; ++i) sH[w][21 + i][lane] += jc[i] * q.g1 + jc[6 + i] * q.g2;
-      sH[w][27][lane] += (float)(gflags & 1);
-      if (a.mask_out != nullptr && valid) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(gflags & 1);
+      sH[w][27][lane] += (float)(gflags & kPixInMask);
+      if (a.mask_out != nullptr && valid) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(gflags & kPixInMask);
       if constexpr (KCH > 0) {
         if (valid) {
           const float md0 = q.m11 * jd0 + q.m12 * jd1, md1 = q.m12 * jd0 + q.m22 * jd1;
@@ -435,191 +431,7 @@ __global__ __launch_bounds__(kBlock, BANET_GATHER_WAVES) void ba_gather_kernel(c
 // --------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------
-constexpr int kStrip8PerWave = 2;     // 8-row strip segments: fewest per resident wave (tools/gpu_r4_k.sh)
-constexpr int kQuadRounds = 12;      // ba_gather128q_kernel: most items per resident wave (measured, profiles/r04_run6_*: wins up to 19200 items -- 640x480 x 1, 160x120 x 8, 80x60 x 32 -- loses at 38400)
-constexpr int kStripSegW = 16, kStripSegH = 32, kStripMinW = 21;   // = kStripW, kStripH, kWinTex of strip_plan.hpp (gather128s.hip)
-constexpr int kGenericBlocksPerCU = BANET_GATHER_WAVES;  // ba_gather_kernel: launch bounds
-constexpr int kC128BlocksPerCU = BANET_G128_WAVES;       // ba_gather128_kernel: launch bounds (LDS: 18 KB)
-
-static bool use_c128(const banet_level_t* lv) {
-  // flags bit 5 (A/B experiments only): force the generic kernel
-  return lv->C == 128 && !lv->tgt_has_grad && !(lv->flags & 32) && (lv->K & 3) == 0 && lv->K <= 256;
-}
-
-int plan_gather(const banet_level_t* lv, GatherPlan* pl) {
-  const int kCUs = num_cus();
-  const int Bsel = lv ? selection_batch(lv) : 0;   // decisions: Bsel; grids and buffer sizes: lv->B
-  if (!lv || lv->B <= 0 || lv->N <= 0 || lv->C <= 0 || lv->K < 0 || lv->H < 4 || lv->W < 4) return BANET_ERR_INVALID_ARG;
-  // (the field was a must-be-zero pad until round 4: anything but the two policies is a caller's garbage, not "throughput")
-  if (lv->policy != BANET_POLICY_THROUGHPUT && lv->policy != BANET_POLICY_BATCH_INVARIANT) return BANET_ERR_INVALID_ARG;
-  if (lv->C > 256 || lv->K > 256) return BANET_ERR_UNSUPPORTED;
-  if (lv->dense && lv->N != lv->H * lv->W) return BANET_ERR_INVALID_ARG;
-  if (lv->dense) {
-    pl->tiles_x = (lv->W + 7) / 8;
-    pl->tiles_y = (lv->H + 7) / 8;
-    pl->tiles = pl->tiles_x * pl->tiles_y;
-  } else {
-    pl->tiles_x = pl->tiles_y = 0;
-    // Sparse points: 64 per wave item -- or 16 (round 6) while four times as many items still fit one resident round: the item is
-    // a serial chain of its points (the reference's own tracker, N = 4096 at batch 1: 64 items = 64 waves on 16 CUs, 54 us per launch)
-    const long long items64 = (long long)((lv->N + kTilePix - 1) / kTilePix) * Bsel * npairs(lv);
-    pl->tile_pts = (4 * items64 <= (long long)kCUs * kGenericBlocksPerCU * kNumWaves && !(lv->flags & 2)) ? 16 : kTilePix;   // bit 1: 64 (A/B)
-    pl->tiles = (lv->N + pl->tile_pts - 1) / pl->tile_pts;
-  }
-  if (lv->dense) pl->tile_pts = kTilePix;
-  pl->groups = (pl->tiles + 3) / 4;
-  pl->c128 = use_c128(lv) ? 1 : 0;
-  // The strip gather (gather128s.hip: 16 x 32-pixel segments, rolling LDS window, target map fetched 1.44 x instead of 2.15 x)
-  // where a launch has at least 4 segments per resident wave (coarser items than the 8x8 tiles: below that the tail of the
-  // last round costs more than the halo saves).  flags bit 18: force it at any size (parity tests); bit 19: off (A/B).
-  pl->strip = 0;
-  pl->strip_fp = 0;
-  if (pl->c128 && lv->dense && !(lv->flags & 524288) && lv->W >= kStripMinW && lv->W < 4096 && lv->H < 4096 &&
-      (size_t)lv->N * lv->C * 4 < ((size_t)1 << 31)) {
-    // segment height: 16 rows.  32-row segments fetch less (target rows 35/32 x instead of 19/16 x: launch 1.12 x vs 1.16 x the
-    // algorithmic bytes) but lose 5 % at every size measured (640x480 x 32: 3396 vs 3230 us, x 256: 27.3 vs 26.1 ms, 5-frame
-    // windows 11.03 vs 10.77 ms; profiles/r03_run11_*, r03_run12_*): half as many, twice as long work items leave a longer
-    // tail in the last round of the queue.  flags bit 21: 32-row segments (A/B, parity tests).
-    const int sxn = (lv->W + kStripSegW - 1) / kStripSegW;
-    // Mid-size two-frame launches (too few 16-row segments per wave, too many pixels for the 4x4-item kernel: 160x120 x 32,
-    // 320x240 x 8 .. 16, 640x480 x 2 .. 4): 8-row segments (target rows 11/8 x) where the launch has at least kStrip8PerWave of
-    // them per resident wave.  flags bits 18 + 10: force them (parity tests); A/B: bit 19 (no strip gather at all).
-    const int np = npairs(lv);
-    const int syn16 = (lv->H + kStripSegH / 2 - 1) / (kStripSegH / 2), syn8 = (lv->H + 7) / 8;
-    const bool force8 = (lv->flags & 262144) && (lv->flags & 1024);
-    const bool low = force8 || (np == 1 && !(lv->flags & ((1 << 21) | 262144)) &&
-                                (long long)sxn * syn16 * Bsel < 4LL * kCUs * 8 &&
-                                (long long)sxn * syn8 * Bsel >= (long long)kStrip8PerWave * kCUs * 8 &&
-                                (long long)((lv->W + 3) / 4) * ((lv->H + 3) / 4) * Bsel > (long long)kQuadRounds * kCUs * 8);
-    const int segh = (lv->flags & (1 << 21)) ? kStripSegH : low ? 8 : kStripSegH / 2;
-    const int syn = (lv->H + segh - 1) / segh;
-    // (A single resident round at tiny batches -- every segment on a wave of its own -- does not pay: one segment is a serial chain
-    // of ~200-270 us whatever the load; batch 1: 640x480 270 vs 272 us, 320x240 205 vs 168 us for the tile kernels.)
-    // multi-frame windows: frame-parallel workgroups (gather128s.hip, FP) -- `pairs` waves per segment, so a launch has
-    // 2048 / pairs resident work-item slots instead of 2048.  flags bit 22: the frames looped over inside one wave (A/B).
-    const bool fp = np >= 2 && np <= 7 && segh == kStripSegH / 2 && !(lv->flags & (1 << 22));
-    const int fp_wg_per_cu = fp ? (int)std::min<size_t>(8 / np, (size_t)(160 * 1024) / (((size_t)np * (7 * 21 * 32 + 128) + 4 * 64 + 4) * 4)) : 0;
-    const long long slots = fp ? (long long)kCUs * fp_wg_per_cu : (long long)kCUs * 8;
-    pl->strip_fp = 0;
-    if ((long long)sxn * syn * Bsel >= 4LL * slots || low || (lv->flags & 262144)) {
-      pl->strip = segh;
-      pl->strip_fp = fp ? 1 : 0;
-      pl->quad = 0;
-      pl->tiles_x = sxn;
-      pl->tiles_y = syn;
-      pl->tiles = sxn * syn;
-      pl->patch = 0;
-      pl->pairloop = 1;
-      pl->qshift = 0;
-      const int resident = fp ? kCUs * fp_wg_per_cu : kCUs * 4;   // 128-thread workgroups, 4 per CU (2 waves per SIMD); FP: by LDS / waves
-      int G = (resident + lv->B - 1) / lv->B;
-      const int want = fp ? pl->tiles : (pl->tiles + 1) / 2;      // one item per wave (FP: per workgroup) at least
-      if (G > want) G = want;
-      if (G < 1) G = 1;
-      pl->G = G;
-      pl->nbands = 1;
-      pl->pstride = kGHdr + lv->C;
-      pl->rows = pl->tiles;
-      pl->frows = pl->rows > kFoldRows ? (pl->rows + kFoldRows - 1) / kFoldRows : pl->rows;
-      const int VBs = lv->B * npairs(lv);
-      const size_t row_bytes_s = (size_t)VBs * pl->pstride * sizeof(float);
-      pl->off_fold = align_up(row_bytes_s * pl->rows, 256);
-      pl->off_queue = pl->off_fold + (pl->frows != pl->rows ? align_up(row_bytes_s * pl->frows, 256) : 0);
-      pl->partial_bytes = pl->off_queue + align_up((size_t)VBs * 8 * sizeof(int), 256);
-      pl->rec_bytes = lv->K > 0 ? align_up((size_t)VBs * lv->N * 8 * sizeof(float), 256) : 0;
-      return BANET_OK;
-    }
-  }
-  // Latency-bound launches (coarse levels, small batches): ba_gather128q_kernel -- 4x4-pixel items, the whole item one step,
-  // ~4x shorter serial chain per item than a tile's 16 steps (gather128q.hip) -- while the launch has at most kQuadRounds items
-  // per resident wave (2 workgroups x 4 waves per CU); beyond that the tile kernels' shared stencils win.
-  // flags bit 25: force it at any size (parity tests, A/B); bit 30: off.
-  pl->quad = 0;
-  if (pl->c128 && lv->dense && !(lv->flags & ((1 << 30) | 512 | 64))) {   // (bits 9 / 6 force the patch / direct tile kernels)
-    const int qxn = (lv->W + 3) / 4, qyn = (lv->H + 3) / 4;
-    const long long qitems = (long long)qxn * qyn * Bsel * npairs(lv);
-    // (multi-frame windows: every virtual window redoes the depth dot -- half the limit: cfg-3's 40x30 x 32 x 4 = 9600 items wins,
-    //  cfg-5's 80x60 x 8 x 7 = 16800 loses 329 vs 210 us, profiles/r04_run9_*)
-    const long long qlimit = (long long)kQuadRounds * kCUs * 8 / (npairs(lv) > 1 ? 2 : 1);
-    if (qitems <= qlimit || (lv->flags & (1 << 25))) {
-      const int VBq = lv->B * npairs(lv);
-      pl->quad = 1;
-      pl->patch = 0;
-      pl->pairloop = 0;
-      pl->qshift = 0;
-      pl->tiles_x = qxn;
-      pl->tiles_y = qyn;
-      pl->tiles = qxn * qyn;
-      int G = (kCUs * 2 + VBq - 1) / VBq;            // one resident round of 256-thread workgroups, 2 per CU
-      const int want = (pl->tiles + kNumWaves - 1) / kNumWaves;
-      if (G > want) G = want;
-      if (G < 1) G = 1;
-      pl->G = G;
-      pl->nbands = 1;
-      pl->pstride = kGHdr + lv->C;
-      pl->rows = pl->tiles;
-      pl->frows = pl->rows > kFoldRows ? (pl->rows + kFoldRows - 1) / kFoldRows : pl->rows;
-      const size_t row_bytes_q = (size_t)VBq * pl->pstride * sizeof(float);
-      pl->off_fold = align_up(row_bytes_q * pl->rows, 256);
-      pl->off_queue = pl->off_fold + (pl->frows != pl->rows ? align_up(row_bytes_q * pl->frows, 256) : 0);
-      pl->partial_bytes = pl->off_queue + align_up((size_t)VBq * 8 * sizeof(int), 256);
-      pl->rec_bytes = lv->K > 0 ? align_up((size_t)VBq * lv->N * 8 * sizeof(float), 256) : 0;
-      return BANET_OK;
-    }
-  }
-  // One resident round: the gather is latency-bound per wave (measured: a second, partial round of
-  // workgroups takes as long as the first), so the grid is what the chip holds at once, split
-  // across the windows.
-  // Large dense levels (>= 4 tiles per resident wave): ba_gather128p_kernel -- wave-private LDS patches with a
-  // software-pipelined box prefetch, 2 workgroups per CU (measured 640x480 x 8: 138 -> 125 us/window, 320x240 x 8:
-  // 48 -> 38); smaller levels are latency-bound and keep the 3-per-CU direct kernel.  flags bit 6: direct (A/B).
-  pl->patch = (pl->c128 && lv->dense && !(lv->flags & 64) &&
-               ((long long)pl->tiles * Bsel * npairs(lv) >= 4LL * kCUs * BANET_G128P_WAVES * kNumWaves ||
-                (lv->flags & 512))) ? 1 : 0;   // bit 9: force it at any size (parity tests)
-  const int resident = kCUs * (pl->patch ? BANET_G128P_WAVES : pl->c128 ? kC128BlocksPerCU : kGenericBlocksPerCU);
-  const int VB = lv->B * npairs(lv);   // virtual windows
-  const int VBsel = Bsel * npairs(lv);
-  // the generic kernel publishes one partial row per WORKGROUP (rows = G), so its grid is part of the arithmetic: taken from Bsel;
-  // the C = 128 kernels publish one row per work item in a fixed place, their grid is free to follow the launch
-  const int Bgrid = pl->c128 ? lv->B : Bsel;
-  // the patch kernel loops over a window's target frames inside a tile (depth dot once per window) where a window alone has
-  // >= 4 tiles per resident wave; below that the 4x coarser items cost more than the shared depth saves (80x60 x 32
-  // windows x 4 frames: 327 -> 478 us) and a work item stays one pair's tile
-  pl->pairloop = (pl->patch && npairs(lv) > 1 && ((long long)pl->tiles * Bsel >= 4LL * kCUs * BANET_G128P_WAVES * kNumWaves ||
-                                                   (lv->flags & 4096))) ? 1 : 0;   // bit 12: force it (parity tests)
-  const int gy = pl->pairloop ? Bgrid : Bgrid * npairs(lv);
-  int target = (resident + gy - 1) / gy;
-  // Mid-size levels (a few tiles per wave at most) start all their waves in the same phase: measured, ~1300 waves
-  // finish a tile in 67 us but 2560 need 169 us (160x120 x 8: one tile per wave 21.1 us/window, two per wave on half
-  // the waves 16.7).  Such levels run on at most 320 workgroups (1280 waves).
-  if (pl->c128 && !pl->patch && (long long)pl->tiles * VBsel < 4LL * kCUs * BANET_G128P_WAVES * kNumWaves)
-    target = min(target, (320 + VB - 1) / VB);
-  // quarter-tile work items pay (measured: 40x30 x 8 windows 94 -> 50 us) only while they still leave the chip
-  // mostly empty -- at most one item per SIMD; beyond that the redone depth dot / geometry costs more than
-  // the shorter step chain saves (80x60 x 8: 101 -> 132 us).  flags bit 4: off (A/B).
-  pl->qshift = (pl->c128 && !pl->patch && pl->tiles <= 32 && (long long)pl->tiles * VBsel * 4 <= (long long)kCUs * 4 &&
-                !(lv->flags & 16)) ? 2 : 0;
-  if (pl->c128 && !pl->patch && (lv->flags & 1024)) pl->qshift = 2;   // bit 10: force quarter tiles (A/B)   // (80x60 x 2 windows, also 640 items, LOSES 82 vs 51 us: coarsest levels only)
-  int G = pl->c128 ? ((pl->tiles << pl->qshift) + 3) / 4 : pl->groups;
-  if (G > target) {
-    G = target >= 8 ? (target & ~7) : target;   // several work items per wave: one resident round, no more
-  } else if (G >= 8) {
-    G = (G + 7) & ~7;   // every item gets its own wave in ONE round (rounding down left a few items for a second
-                        // pass: 2x the latency of a level that is pure latency); surplus workgroups find nothing and exit
-  }
-  if (G < 1) G = 1;
-  pl->G = G;
-  pl->nbands = (G & 7) == 0 ? 8 : 1;
-  pl->pstride = kGHdr + lv->C;
-  pl->rows = pl->c128 ? (pl->tiles << pl->qshift) : G;
-  pl->frows = pl->rows > kFoldRows ? (pl->rows + kFoldRows - 1) / kFoldRows : pl->rows;
-  const size_t row_bytes = (size_t)VB * pl->pstride * sizeof(float);
-  pl->off_fold = align_up(row_bytes * pl->rows, 256);
-  pl->off_queue = pl->off_fold + (pl->frows != pl->rows ? align_up(row_bytes * pl->frows, 256) : 0);
-  pl->partial_bytes = pl->off_queue + align_up((size_t)VB * 8 * sizeof(int), 256);
-  pl->rec_bytes = lv->K > 0 ? align_up((size_t)VB * lv->N * 8 * sizeof(float), 256) : 0;
-  return BANET_OK;
-}
+// (plan_gather -- which kernel, what grid, the partial buffer's layout: plan.hpp)
 
 // sum kFoldRows consecutive partial rows (fixed order) -> one row
 __global__ __launch_bounds__(256) void ba_fold_kernel(const float* __restrict__ in, int rows, int stride,

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128_WAVES) void ba_gather128_kernel(
       }
       const bool interior = (x0 >= 1) && (x0 + 2 <= W - 1) && (y0 >= 1) && (y0 + 2 <= H - 1);
       const bool fast = m && interior;
-      gflags = (m ? 1 : 0) | (fast ? 2 : 0) | ((m && !fast) ? 4 : 0);
+      gflags = (m ? kPixInMask : 0) | (fast ? kPixFast : 0) | ((m && !fast) ? kPixRim : 0);
       gx0 = x0;
       gy0 = y0;
       // parameters of the branch-free gather: non-fast pixels read the safe texel (1,1) with
@@ -270,8 +270,8 @@ __global__ __launch_bounds__(kBlock, BANET_G128_WAVES) void ba_gather128_kernel(
       const int j = 4 * s + grp;
       const float4 pa = *reinterpret_cast<const float4*>(&sPar[w][j][0]);
       const float4 pb = *reinterpret_cast<const float4*>(&sPar[w][j][4]);
-#ifdef BANET_ABLATE   // development aid (tools/prof_assemble.py): flags bit 0 -> every tap reads texel (1,1) / point 0
-      const bool abl = (lv.flags & 1) != 0;
+#ifdef BANET_ABLATE   // development aid (tools/prof_assemble.py): kDevAblateTaps -> every tap reads texel (1,1) / point 0
+      const bool abl = (lv.flags & kDevAblateTaps) != 0;
       const unsigned osrc = abl ? 0u : (unsigned)__float_as_int(pa.x), oa = abl ? (unsigned)((W + 1) * C) : (unsigned)__float_as_int(pa.y);
 #else
       const unsigned osrc = (unsigned)__float_as_int(pa.x), oa = (unsigned)__float_as_int(pa.y);
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128_WAVES) void ba_gather128_kernel(
     }
     {
       // patch the pixels whose stencil touches the image rim (rare): generic slow routine
-      unsigned long long slow = __ballot((gflags & 4) != 0 && mine);
+      unsigned long long slow = __ballot((gflags & kPixRim) != 0 && mine);
       while (slow) {  // wave-uniform
         const int j = __builtin_ctzll(slow);
         slow &= slow - 1;
@@ -396,8 +396,8 @@ __global__ __launch_bounds__(kBlock, BANET_G128_WAVES) void ba_gather128_kernel(
         }
 #pragma unroll
       for (int i = 0; i < 6; ++i) carry_push_n<5, 32>(pend, jc[i] * q.g1 + jc[6 + i] * q.g2, 21 + i);
-      carry_push_n<5, 32>(pend, (float)(gflags & 1), 27);
-      if (a.mask_out != nullptr && valid && mine) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(gflags & 1);
+      carry_push_n<5, 32>(pend, (float)(gflags & kPixInMask), 27);
+      if (a.mask_out != nullptr && valid && mine) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(gflags & kPixInMask);
 #pragma unroll
       for (int i = 28; i < 32; ++i) carry_push_n<5, 32>(pend, 0.f, i);
       float tot = pend[5];

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
   const int grp = lane >> 4, sub = lane & 15;
   const int half = lane >> 5, li = lane & 31;
 
-#ifdef BANET_ABLATE   // development aid (tools/prof_assemble.py): flags bits 0..3 switch phases of this kernel off
+#ifdef BANET_ABLATE   // development aid (tools/prof_assemble.py): the kDevAblate* bits switch phases of this kernel off
   const int abl = lv.flags;
 #else
   constexpr int abl = 0;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
   // the first tiles (depth-dot burst, then every unit's loads at the same time); measured 320x240 x 8: 39.0 -> 37.6
   // us/window, 640x480 x 8: 125.5 -> 124.1; 15 us per wave: no better.  (On the short levels, which run the direct
   // kernel, any stagger loses.)
-  if (!(lv.flags & 2048))   // bit 11: no stagger (A/B)
+  if (!(lv.flags & kDevPatchNoStagger))   // no stagger (A/B)
     for (int i = 0; i < 2 * w; ++i) __builtin_amdgcn_s_sleep(127);
   if constexpr (KV4 > 0) {
 #pragma unroll
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
     // (16 B per lane); 32 row pairs go through a 5-level transposing butterfly inside each half,
     // leaf t of half h carrying pixel h*32 + brev5p(t), so that pixel j's sum lands on lane j.
     float D = valid ? dep_b[pt] : 0.f;
-    if (KV4 > 0 && !(abl & 4)) {
+    if (KV4 > 0 && !(abl & kDevAblateDepthDot)) {
       float pend[6];
       float part[32];   // all 32 row loads of the half wave in flight together (2 waves per SIMD: 256 VGPRs)
 #pragma unroll
@@ -302,14 +302,14 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
       }
       const bool interior = (x0 >= 1) && (x0 + 2 <= W - 1) && (y0 >= 1) && (y0 + 2 <= H - 1);
       const bool fast = m && interior;
-      gflags = (m ? 1 : 0) | (fast ? 2 : 0) | ((m && !fast) ? 4 : 0);
+      gflags = (m ? kPixInMask : 0) | (fast ? kPixFast : 0) | ((m && !fast) ? kPixRim : 0);
       gx0 = x0;
       gy0 = y0;
     };
     pixel_geometry();
     {
       const int x0 = gx0, y0 = gy0;
-      const bool fast = (gflags & 2) != 0;
+      const bool fast = (gflags & kPixFast) != 0;
       // parameters of the branch-free gather: non-fast pixels read the safe texel (1,1) with
       // zero weights
       const float mk = fast ? 1.f : 0.f;
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
         const int bx0 = red8(fast ? x0 : big, false), bx1 = red8(fast ? x0 : -big, true);
         const int by0 = red8(fast ? y0 : big, false), by1 = red8(fast ? y0 : -big, true);
         const int x_lo = bx0 - 1, y_lo = by0 - 1, pw = bx1 - bx0 + 4, ph = by1 - by0 + 4;
-        const bool st = bx1 >= bx0 && (FS ? (pw <= 8 && ph <= 5) : pw * ph <= PT) && !(lv.flags & 128);
+        const bool st = bx1 >= bx0 && (FS ? (pw <= 8 && ph <= 5) : pw * ph <= PT) && !(lv.flags & kDevPatchNoStaging);
         pb.w = __int_as_float(((fast ? y0 - y_lo : 1) * (FS ? 8 : pw) + (fast ? x0 - x_lo : 1)) * 64);
         if ((lane & (GL - 1)) == 0) {
           sGrp[w][lane / GL][0] = st ? (y_lo * W + x_lo) * C : 0;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
           unsigned off = (unsigned)gb + (unsigned)((min(row, ph_ - 1) * W + col) * C) + 4u * (unsigned)sub + 64u * (unsigned)h_;
-          if (abl & 1) off = 4u * (unsigned)sub + 64u * (unsigned)h_ + (unsigned)((lane >> 4) * C);   // every box = texels 0..3
+          if (abl & kDevAblateTaps) off = 4u * (unsigned)sub + 64u * (unsigned)h_ + (unsigned)((lane >> 4) * C);   // every box = texels 0..3
           pst[i] = *reinterpret_cast<const f32x4*>(tgt_b + (size_t)off);
           col += 4;
           if (col >= pw_) {
@@ -397,15 +397,15 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
 #pragma unroll
         for (int t = 0; t < US; ++t) {
           unsigned osrc = (unsigned)__float_as_int(sPar[w][4 * (US * sp_ + t) + grp][0]);
-          if (abl & 2) osrc = (unsigned)(grp * C);                                                        // every source row = pixels 0..3
+          if (abl & kDevAblateSourceRows) osrc = (unsigned)(grp * C);                                                        // every source row = pixels 0..3
           pf1[t] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src_b + (size_t)(osrc + 64u * (unsigned)h_ + 4u * sub)));
         }
       }
     };
     const int sp_end = s_hi / US;
-    // unit order: 0..7 = left / right unit of pixel rows 0-1, 2-3, ... (Z order); flags bit 17 (experiment, US = 2 only):
+    // unit order: 0..7 = left / right unit of pixel rows 0-1, 2-3, ... (Z order); kDevPatchColumnMajor (experiment, US = 2 only):
     // the left column top to bottom, then the right column bottom to top -- horizontal neighbours 1..7 units apart instead of 1
-    const bool colmajor = US == 2 && (lv.flags & 131072) != 0;
+    const bool colmajor = US == 2 && (lv.flags & kDevPatchColumnMajor) != 0;
     auto unit_at = [&](int it) { return colmajor ? (it < 4 ? 2 * it : 2 * (7 - it) + 1) : it; };
     for (int it = s_lo / US; it < sp_end; ++it) {
       const int sp = unit_at(it);
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
           BANET_TICK(tu1);   // (the tick waits for the LDS writes of the box)
           BANET_TACC(tp_stage, tu0, tu1);
 #endif
-          if (!(abl & 8))
+          if (!(abl & kDevAblateGather))
 #pragma unroll
           for (int t = 0; t < US; ++t) {
             const int j = 4 * (US * sp + t) + grp;
@@ -516,7 +516,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
     }
     {
       // patch the pixels whose stencil touches the image rim (rare): generic slow routine
-      unsigned long long slow = __ballot((gflags & 4) != 0 && mine);
+      unsigned long long slow = __ballot((gflags & kPixRim) != 0 && mine);
       while (slow) {  // wave-uniform
         const int j = __builtin_ctzll(slow);
         slow &= slow - 1;
@@ -564,8 +564,8 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
         }
 #pragma unroll
       for (int i = 0; i < 6; ++i) carry_push_p<5, 32>(pend, jc[i] * q.g1 + jc[6 + i] * q.g2, 21 + i);
-      carry_push_p<5, 32>(pend, (float)(gflags & 1), 27);
-      if (a.mask_out != nullptr && valid && mine) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(gflags & 1);
+      carry_push_p<5, 32>(pend, (float)(gflags & kPixInMask), 27);
+      if (a.mask_out != nullptr && valid && mine) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(gflags & kPixInMask);
 #pragma unroll
       for (int i = 28; i < 32; ++i) carry_push_p<5, 32>(pend, 0.f, i);
       float tot = pend[5];
@@ -628,15 +628,15 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
 
 int launch_gather128p(const GatherArgs& a, int K, hipStream_t s) {
   dim3 grid(a.G, a.pairloop ? a.lv.B : a.lv.B * a.pairs), block(kBlock);
-  // flags bit 13 (A/B experiment, experiments/README.md): 60 KB of unused dynamic LDS per workgroup -> ONE workgroup per CU
+  // kDevPatchOnePerCU (A/B experiment, experiments/README.md): 60 KB of unused dynamic LDS per workgroup -> ONE workgroup per CU
   // (one gather wave per SIMD), the occupancy a wave-specialised gather + MFMA-accumulator kernel would leave the gather
   size_t dyn = 0;
-  if (a.lv.flags & 8192) {
+  if (a.lv.flags & kDevPatchOnePerCU) {
     dyn = 60 * 1024;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_gather128p_kernel<1, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
   }
-  const bool u4 = (a.lv.flags & 16384) != 0;   // bit 14: 4-step units (A/B, experiments/README.md)
-  const bool packed = (a.lv.flags & 65536) != 0;   // bit 16: the packed patch with flat loads (A/B)
+  const bool u4 = (a.lv.flags & kDevPatchUnits4) != 0;   // 4-step units (A/B, experiments/README.md)
+  const bool packed = (a.lv.flags & kDevPatchPacked) != 0;   // the packed patch with flat loads (A/B)
   const bool small = (size_t)a.lv.H * a.lv.W * a.lv.C * 4 < ((size_t)1 << 31) && (size_t)a.lv.N * a.lv.C * 4 < ((size_t)1 << 31);
   const bool fs = small && !packed && !dyn;          // the fixed-stride patch addresses the maps with 32-bit buffer offsets
   if (K == 0 && fs)

@@ -20,7 +20,7 @@
 //   * items are assigned statically (wave g of the launch takes items g, g + waves, ...: they cost the same), no atomic queue:
 //     at one window the queue's single counter was popped 2 x items times and serialised the launch.
 // Same arithmetic per pixel as ba_gather128_kernel; the channel sums are added unit by unit (different rounding order).
-// Selected by plan_gather for launches with few items per resident wave (flags bit 25 forces it, bit 30 disables it).
+// Selected by plan_gather for launches with few items per resident wave (kDevForceQuadGather forces it, kDevNoQuadGather disables it).
 #include "quad_common.hpp"
 
 namespace banet {
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherAr
     // ---- 2. geometry (every lane of the quad computes its pixel's) -----------------------------------------------------------
     SGeo ge;
     strip_geometry(lv, pq, valid, px, py, D, ge);
-    const bool fast = (ge.flags & 2) != 0;
+    const bool fast = (ge.flags & kPixFast) != 0;
     const float mk = fast ? 1.f : 0.f;
     const float w00 = mk * ((1.f - ge.dx) * (1.f - ge.dy)), w01 = mk * (ge.dx * (1.f - ge.dy)), w10 = mk * ((1.f - ge.dx) * ge.dy),
                 w11 = mk * (ge.dx * ge.dy);
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherAr
     // ---- 4. pixels whose stencil touches the image rim (rare): the generic slow routine, one pixel at a time ------------------
     float absd2[1][2] = {{0.f, 0.f}};   // channels 2 lane, 2 lane + 1
     {
-      unsigned long long slow = __ballot((ge.flags & 4) != 0 && q == 0);
+      unsigned long long slow = __ballot((ge.flags & kPixRim) != 0 && q == 0);
       while (slow) {   // wave-uniform
         const int j = __builtin_ctzll(slow);
         slow &= slow - 1;
@@ -231,14 +231,14 @@ __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherAr
         }
 #pragma unroll
       for (int i = 0; i < 6; ++i) carry_push_s<5, 32>(pend, own ? jc[i] * qv.g1 + jc[6 + i] * qv.g2 : 0.f, 21 + i);
-      carry_push_s<5, 32>(pend, own ? (float)(ge.flags & 1) : 0.f, 27);
+      carry_push_s<5, 32>(pend, own ? (float)(ge.flags & kPixInMask) : 0.f, 27);
 #pragma unroll
       for (int i = 28; i < 32; ++i) carry_push_s<5, 32>(pend, 0.f, i);
       float tot = pend[5];
       tot += dpp_mov<kDppXor1>(tot);
       const int leaf = brev5s(lane >> 1);
       if ((lane & 1) == 0 && leaf < 28) part[leaf] = tot;
-      if (a.mask_out != nullptr && valid && own) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(ge.flags & 1);
+      if (a.mask_out != nullptr && valid && own) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(ge.flags & kPixInMask);
       if constexpr (KV4 > 0) {
         if (valid && own) {
           const float md0 = qv.m11 * ge.jd0 + qv.m12 * ge.jd1, md1 = qv.m12 * ge.jd0 + qv.m22 * ge.jd1;

@@ -28,6 +28,7 @@
 
 #include "quad_common.hpp"
 #include "strip_plan.hpp"
+static_assert(banet::kStripSegW == banet::kStripW && banet::kStripSegH == banet::kStripH && banet::kStripMinW == banet::kWinTex, "plan.hpp sizes the strip launch by these");
 
 #ifndef BANET_STRIP_OPT_DEFAULT
 #define BANET_STRIP_OPT_DEFAULT 0
@@ -407,7 +408,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
         const bool valid = (px < W) && (py < H);
         SGeo ge;
         strip_geometry(lv, pq, valid, px, py, Dv[hh][c4], ge);
-        const bool fast = (ge.flags & 2) != 0;
+        const bool fast = (ge.flags & kPixFast) != 0;
         const int m7 = fast ? (ge.y0 - 1) % kWinRows : 0;
         P0v[hh][c4] = (fast ? (ge.x0 | (ge.y0 << 12)) : 0) | (m7 << 24) | (fast ? (1 << 27) : 0);
         DXv[hh][c4] = ge.dx;
@@ -459,7 +460,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
         ncol3 = 8 * max(rfl(xe) + 1 - 16, 1);
         mask3 = ncol3 >= 64 ? ~0ull : ((1ull << ncol3) - 1ull);
         strip_plan_dynamic(env, SEGH, rfl(ye));
-        if (lv.flags & (1 << 20)) {   // parity tests: every pixel row takes the direct (window-less) path
+        if (lv.flags & kDevStripDirectRows) {   // parity tests: every pixel row takes the direct (window-less) path
           if (step_mode(env.ctlv) == kStepWindow) env.ctlv = kStepDirect;
         }
         plan_ctl = env.ctlv;
@@ -704,7 +705,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
         qv.g2 = Q4[hh][c4];
         {
           // patch the pixels whose stencil touches the image rim (rare): generic slow routine
-          unsigned long long slow = __ballot((ge.flags & 4) != 0);
+          unsigned long long slow = __ballot((ge.flags & kPixRim) != 0);
           while (slow) {  // wave-uniform
             const int j = __builtin_ctzll(slow);
             slow &= slow - 1;
@@ -744,8 +745,8 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
             }
 #pragma unroll
           for (int i = 0; i < 6; ++i) accp[21 + i] += jc[i] * qv.g1 + jc[6 + i] * qv.g2;
-          accp[27] += (float)(ge.flags & 1);
-          if (a.mask_out != nullptr && valid) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(ge.flags & 1);
+          accp[27] += (float)(ge.flags & kPixInMask);
+          if (a.mask_out != nullptr && valid) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(ge.flags & kPixInMask);
         }
 
         if constexpr (KV4 > 0) {

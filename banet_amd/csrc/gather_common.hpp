@@ -26,6 +26,13 @@ struct GatherArgs {
   int tile_pts;     // ba_gather_kernel, sparse points: points per wave item (64 or 16)
 };
 
+// per-pixel geometry bits of the gather kernels (`gflags`, QuadGeo::flags)
+enum : int {
+  kPixInMask = 1,   // the projection falls inside the target image
+  kPixFast = 2,     // ... and its whole stencil does (3C map: always): the main loop's taps
+  kPixRim = 4,      // in the mask but on the rim: patched by the slow path
+};
+
 template <int VEC>
 struct Vec {
   float v[VEC];
@@ -191,12 +198,7 @@ __device__ __noinline__ Q5 border_pixel_q5(int x0, int y0, float w00, float w01,
   return q;
 }
 
-#ifndef BANET_G128P_WAVES
-#define BANET_G128P_WAVES 2   // ba_gather128p_kernel: workgroups per CU (its prefetch registers need 256 VGPRs)
-#endif
-#ifndef BANET_G128_WAVES
-#define BANET_G128_WAVES 3   // ba_gather128_kernel: workgroups per CU (= waves per SIMD) of its launch bounds
-#endif
+// (BANET_G128_WAVES / BANET_G128P_WAVES, the workgroups per CU of the launch bounds: plan.hpp)
 int launch_gather128(const GatherArgs& a, int K, hipStream_t s);
 int launch_gather128p(const GatherArgs& a, int K, hipStream_t s);   // gather128p.hip: wave-private LDS patches
 int launch_gather128s(const GatherArgs& a, int K, hipStream_t s);   // gather128s.hip: strip segments, rolling LDS window

@@ -1,41 +1,17 @@
-// Host-visible plans / argument blocks shared by the translation units of libbanet_hip.so.
+// Launchers / argument blocks shared by the translation units of libbanet_hip.so (the host-only launch plans: plan.hpp).
 #pragma once
 #include "common.hpp"
 
 namespace banet {
 
-constexpr int kGHdr = 32;       // gather partial header: 21 H_cc + 6 Atb_c + nvalid (+pad), then C x sum|d|
 constexpr int kUStrideS = 8;    // per-pixel record: u0..u5, s, r
-
-inline int npairs(const banet_level_t* lv) { return lv->pairs > 1 ? lv->pairs : 1; }
-// the batch size every kernel / arithmetic-form / partial-row decision is taken from (banet_level_t.policy): the launch's own, or
-// -- BANET_POLICY_BATCH_INVARIANT -- the canonical one, so that a window's bits do not depend on who shares its launch
-inline int selection_batch(const banet_level_t* lv) { return lv->policy == BANET_POLICY_BATCH_INVARIANT ? BANET_CANONICAL_BATCH : lv->B; }
 
 // compute units of the current device (hipDeviceAttributeMultiprocessorCount, queried once per device; 256 = MI355X when no
 // device is visible, e.g. the host-only plan / workspace arithmetic of the CPU tests).  The launch plans size their grids by it.
 int num_cus();
 
 // ---- gather.hip ------------------------------------------------------------------------
-struct GatherPlan {
-  int G, tiles, tiles_x, tiles_y, groups, pstride;
-  int c128;     // 1: ba_gather128_kernel (dynamic tile queue, one partial row per tile)
-  int patch;    // 1: ba_gather128p_kernel (same interface; taps from wave-private LDS patches) for large levels
-  int strip;    // ba_gather128s_kernel (work items = 16-pixel-wide strip segments, rolling LDS window): pixel rows per segment
-                //    (32 or 16; 0 = another kernel); tiles_x / tiles_y / tiles then count segments
-  int quad;     // 1: ba_gather128q_kernel (work items = 4x4 pixel blocks, one step per item): latency-bound launches; tiles_x / tiles_y / tiles count items
-  int strip_fp; // strip kernel, multi-frame windows: a workgroup = `pairs` waves on one segment, wave p against target frame p
-  int rows;     // partial rows per window written by the gather kernel (tiles or G)
-  int frows;    // rows per window handed to ba_reduce2_kernel (after ba_fold_kernel when rows > kFoldRows)
-  int nbands;   // tile-queue bands (8 = one per XCD)
-  int pairloop; // patch kernel: target frames looped over inside a tile (grid y = windows)
-  int qshift;   // 2: quarter-tile work items (levels with fewer tiles than resident waves)
-  int tile_pts; // generic kernel, sparse points: points per wave item (64; 16 on latency-bound launches)
-  size_t off_fold, off_queue;   // inside the partial region
-  size_t partial_bytes, rec_bytes;
-};
-constexpr int kFoldRows = 64;
-int plan_gather(const banet_level_t* lv, GatherPlan* pl);
+// (GatherPlan / plan_gather: plan.hpp)
 // prepare (reset the tile queue) -> launch (the gather kernel alone: this is what the profiler times)
 // -> finish (fold the tile partials); `reduced` returns the rows ba_reduce2_kernel should read
 void prepare_gather(const banet_level_t* lv, const GatherPlan& pl, float* partials, hipStream_t s);
@@ -54,22 +30,10 @@ struct MlpRole {        // one extra workgroup per window of the SYRK launch eva
   float Nf;             // residual rows per window (N * pairs)
   float* y;             // [B] MLP output
 };
-struct SyrkPlan {
-  int Gs, tiles, pstride, nb;
-  int x3;       // ba_syrk_bf16x6_kernel, opt-in: three products instead of six (flags bit 29)
-  int direct;   // 0: the LDS-tiled kernel, 1: ba_syrk_direct_kernel (fp32 MFMA, A/B), 2: ba_syrk_bf16x6_kernel (K = 64 / 128, <= 4 frames),
-                // 3: syrk_wide.hip jobs (K = 256, or K = 128 with more than 4 target frames)
-  int f16;      // ba_syrk_bf16x6_kernel: the fp16 two-piece form is eligible (plan_syrk); f16_standalone: also in a single assembly pass
-  int f16_standalone;
-  size_t off_colmax, off_recmax;   // f16: [B][K] basis column maxima, [B][32][2] record maxima, inside the partial buffer
-  size_t off_aux;        // direct == 3: per-pixel (s, r) sums over the frames, inside the partial buffer
-  size_t partial_bytes;
-};
-size_t syrk_wide_aux_bytes(int B, int N, int pairs);
+// (SyrkPlan / plan_syrk / syrk_wide_aux_bytes: plan.hpp)
 int launch_syrk_wide(const float* basis, const float* rec, int B, int N, int K, int pairs, int Gs, int pstride,
                      const int32_t* active, int active_stride, float* partials, float* aux, hipStream_t s,
                      const float* colmax = nullptr, const float* recmax = nullptr);   // both given: the fp16 two-piece form
-int plan_syrk(int B, int Bsel, int N, int K, int pairs, int dbg, SyrkPlan* pl);   // Bsel: the batch the decisions are taken from (selection_batch)
 int launch_syrk(const float* basis, const float* rec, int B, int N, int K, int pairs, const SyrkPlan& pl,
                 const int32_t* active, int active_stride, float* partials, hipStream_t s, const MlpRole* mr = nullptr,
                 int f16_stats = -1);   // f16_stats: -1 = exact bf16 form; 0 / 1 = fp16 two-piece form (pl.f16), basis column maxima to compute / in
@@ -80,14 +44,7 @@ void launch_reduce2(const float* gpart, int Gg, int gstride, const float* spart,
                     float* absres, float* nvalid, hipStream_t s);
 
 // ---- assemble.hip: one assembly pass = gather + syrk + reduce ------------------------------
-struct AsmPlan {
-  GatherPlan g;
-  SyrkPlan s;
-  int P;
-  size_t ws_bytes;      // gather partials + records + syrk partials
-  size_t off_rec, off_spart;
-};
-int plan_assemble(const banet_level_t* lv, AsmPlan* pl);
+// (AsmPlan / plan_assemble: plan.hpp)
 int launch_assemble(const banet_level_t* lv, const AsmPlan& pl, const float* R, const float* T, const float* Wc,
                     const int32_t* active, int active_stride, void* ws, float* AtA, float* Atb, float* absres,
                     float* nvalid, hipStream_t s, bool reset_queue = true, const banet_mlp_t* role_mlp = nullptr,
@@ -167,7 +124,7 @@ struct SolveArgs {
   int nqueue;  // words per window
   const float* mlp_y;   // [B] lambda-MLP outputs precomputed by the SYRK launch's role workgroups, or nullptr
   banet_lm_params_t lm;   // run-time LM configuration (legacy/ba.py:5-9)
-  int flags;              // banet_level_t.flags (development switches: bit 23 = blocked LDL^T only, no conjugate gradients)
+  int flags;              // banet_level_t.flags (development switches: kDevSolveLdltOnly)
 };
 int launch_solve(const SolveArgs& a, hipStream_t s);
 int launch_spd_solve(const float* A, const float* rhs, float* x, int B, int P, hipStream_t s);   // 32 <= P, matrix in LDS

@@ -1,0 +1,342 @@
+// The host-side launch plans of one assembly pass: which gather / SYRK kernel runs, on what grid, how many partial rows it
+// writes (the summation tree) and where every buffer lies in the workspace.  Host-only, plain C++17 (no HIP include): the .hip
+// files take the plans AND the occupancy numbers of their __launch_bounds__ from here, and tests/native/plan_host.cpp
+// compiles this header with g++ to pin every decision (tests/test_plan_cpu.py).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/banet_hip.h"
+#include "dev_flags.hpp"
+
+// workgroups per CU (= waves per SIMD) the gather kernels are compiled for: their __launch_bounds__ and the plans' resident rounds
+#ifndef BANET_GATHER_WAVES
+#define BANET_GATHER_WAVES 3   // ba_gather_kernel
+#endif
+#ifndef BANET_G128P_WAVES
+#define BANET_G128P_WAVES 2   // ba_gather128p_kernel: workgroups per CU (its prefetch registers need 256 VGPRs)
+#endif
+#ifndef BANET_G128_WAVES
+#define BANET_G128_WAVES 3   // ba_gather128_kernel: workgroups per CU (= waves per SIMD) of its launch bounds
+#endif
+
+namespace banet {
+
+constexpr int kWave = 64;         // CDNA wavefront
+constexpr int kTilePix = 64;      // source pixels per workgroup tile (8x8 patch in dense mode)
+constexpr int kBlock = 256;       // 4 waves
+constexpr int kNumWaves = kBlock / kWave;
+constexpr int kGHdr = 32;         // gather partial header: 21 H_cc + 6 Atb_c + nvalid (+pad), then C x sum|d|
+constexpr int kFoldRows = 64;     // ba_fold_kernel sums this many consecutive partial rows into one
+constexpr int kRecMaxBlocks = 32; // workgroups per window of the fp16 SYRK's record-maxima pre-pass
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Bump allocator of the workspace layouts: 256-byte aligned offsets in the order of the take() calls; `off` ends as the total.
+struct Arena {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t at = off;
+    off = align_up(off + bytes, 256);
+    return at;
+  }
+};
+
+inline int npairs(const banet_level_t* lv) { return lv->pairs > 1 ? lv->pairs : 1; }
+// the batch size every kernel / arithmetic-form / partial-row decision is taken from (banet_level_t.policy): the launch's own, or
+// -- BANET_POLICY_BATCH_INVARIANT -- the canonical one, so that a window's bits do not depend on who shares its launch
+inline int selection_batch(const banet_level_t* lv) { return lv->policy == BANET_POLICY_BATCH_INVARIANT ? BANET_CANONICAL_BATCH : lv->B; }
+
+// ---- gather ----------------------------------------------------------------------------
+struct GatherPlan {
+  int G, tiles, tiles_x, tiles_y, groups, pstride;
+  int c128;     // 1: ba_gather128_kernel (dynamic tile queue, one partial row per tile)
+  int patch;    // 1: ba_gather128p_kernel (same interface; taps from wave-private LDS patches) for large levels
+  int strip;    // ba_gather128s_kernel (work items = 16-pixel-wide strip segments, rolling LDS window): pixel rows per segment
+                //    (32 or 16; 0 = another kernel); tiles_x / tiles_y / tiles then count segments
+  int quad;     // 1: ba_gather128q_kernel (work items = 4x4 pixel blocks, one step per item): latency-bound launches; tiles_x / tiles_y / tiles count items
+  int strip_fp; // strip kernel, multi-frame windows: a workgroup = `pairs` waves on one segment, wave p against target frame p
+  int rows;     // partial rows per window written by the gather kernel (tiles or G)
+  int frows;    // rows per window handed to ba_reduce2_kernel (after ba_fold_kernel when rows > kFoldRows)
+  int nbands;   // tile-queue bands (8 = one per XCD)
+  int pairloop; // patch kernel: target frames looped over inside a tile (grid y = windows)
+  int qshift;   // 2: quarter-tile work items (levels with fewer tiles than resident waves)
+  int tile_pts; // generic kernel, sparse points: points per wave item (64; 16 on latency-bound launches)
+  size_t off_fold, off_queue;   // inside the partial region
+  size_t partial_bytes, rec_bytes;
+};
+
+constexpr int kStrip8PerWave = 2;     // 8-row strip segments: fewest per resident wave (tools/gpu_r4_k.sh)
+constexpr int kQuadRounds = 12;      // ba_gather128q_kernel: most items per resident wave (measured, profiles/r04_run6_*: wins up to 19200 items -- 640x480 x 1, 160x120 x 8, 80x60 x 32 -- loses at 38400)
+constexpr int kStripSegW = 16, kStripSegH = 32, kStripMinW = 21;   // = kStripW, kStripH, kWinTex of strip_plan.hpp (asserted in gather128s.hip)
+constexpr int kGenericBlocksPerCU = BANET_GATHER_WAVES;  // ba_gather_kernel: launch bounds
+constexpr int kC128BlocksPerCU = BANET_G128_WAVES;       // ba_gather128_kernel: launch bounds (LDS: 18 KB)
+constexpr int kPatchBlocksPerCU = BANET_G128P_WAVES;     // ba_gather128p_kernel: launch bounds
+
+namespace plan_detail {
+
+inline bool use_c128(const banet_level_t* lv) {
+  return lv->C == 128 && !lv->tgt_has_grad && !(lv->flags & kDevGenericGather) && (lv->K & 3) == 0 && lv->K <= 256;
+}
+
+// The strip gather (gather128s.hip: 16 x 32-pixel segments, rolling LDS window, target map fetched 1.44 x instead of 2.15 x)
+// where a launch has at least 4 segments per resident wave (coarser items than the 8x8 tiles: below that the tail of the
+// last round costs more than the halo saves).  kDevForceStripGather: at any size (parity tests); kDevNoStripGather: off (A/B).
+inline bool choose_strip(const banet_level_t* lv, int kCUs, int Bsel, GatherPlan* pl) {
+  if (!(pl->c128 && lv->dense && !(lv->flags & kDevNoStripGather) && lv->W >= kStripMinW && lv->W < 4096 && lv->H < 4096 &&
+        (size_t)lv->N * lv->C * 4 < ((size_t)1 << 31)))
+    return false;
+  // segment height: 16 rows.  32-row segments fetch less (target rows 35/32 x instead of 19/16 x: launch 1.12 x vs 1.16 x the
+  // algorithmic bytes) but lose 5 % at every size measured (640x480 x 32: 3396 vs 3230 us, x 256: 27.3 vs 26.1 ms, 5-frame
+  // windows 11.03 vs 10.77 ms; profiles/r03_run11_*, r03_run12_*): half as many, twice as long work items leave a longer
+  // tail in the last round of the queue.  kDevStripRows32: 32-row segments (A/B, parity tests).
+  const int sxn = (lv->W + kStripSegW - 1) / kStripSegW;
+  // Mid-size two-frame launches (too few 16-row segments per wave, too many pixels for the 4x4-item kernel: 160x120 x 32,
+  // 320x240 x 8 .. 16, 640x480 x 2 .. 4): 8-row segments (target rows 11/8 x) where the launch has at least kStrip8PerWave of
+  // them per resident wave.  kDevForceStripGather + kDevQuarterTiles: force them (parity tests); A/B: kDevNoStripGather (no strip gather at all).
+  const int np = npairs(lv);
+  const int syn16 = (lv->H + kStripSegH / 2 - 1) / (kStripSegH / 2), syn8 = (lv->H + 7) / 8;
+  const bool force8 = (lv->flags & kDevForceStripGather) && (lv->flags & kDevQuarterTiles);
+  const bool low = force8 || (np == 1 && !(lv->flags & (kDevStripRows32 | kDevForceStripGather)) &&
+                              (long long)sxn * syn16 * Bsel < 4LL * kCUs * 8 &&
+                              (long long)sxn * syn8 * Bsel >= (long long)kStrip8PerWave * kCUs * 8 &&
+                              (long long)((lv->W + 3) / 4) * ((lv->H + 3) / 4) * Bsel > (long long)kQuadRounds * kCUs * 8);
+  const int segh = (lv->flags & kDevStripRows32) ? kStripSegH : low ? 8 : kStripSegH / 2;
+  const int syn = (lv->H + segh - 1) / segh;
+  // (A single resident round at tiny batches -- every segment on a wave of its own -- does not pay: one segment is a serial chain
+  // of ~200-270 us whatever the load; batch 1: 640x480 270 vs 272 us, 320x240 205 vs 168 us for the tile kernels.)
+  // multi-frame windows: frame-parallel workgroups (gather128s.hip, FP) -- `pairs` waves per segment, so a launch has
+  // 2048 / pairs resident work-item slots instead of 2048.  kDevStripFrameLoop: the frames looped over inside one wave (A/B).
+  const bool fp = np >= 2 && np <= 7 && segh == kStripSegH / 2 && !(lv->flags & kDevStripFrameLoop);
+  const int fp_wg_per_cu = fp ? (int)std::min<size_t>(8 / np, (size_t)(160 * 1024) / (((size_t)np * (7 * 21 * 32 + 128) + 4 * 64 + 4) * 4)) : 0;
+  const long long slots = fp ? (long long)kCUs * fp_wg_per_cu : (long long)kCUs * 8;
+  if (!((long long)sxn * syn * Bsel >= 4LL * slots || low || (lv->flags & kDevForceStripGather))) return false;
+  pl->strip = segh;
+  pl->strip_fp = fp ? 1 : 0;
+  pl->tiles_x = sxn;
+  pl->tiles_y = syn;
+  pl->tiles = sxn * syn;
+  pl->pairloop = 1;
+  const int resident = fp ? kCUs * fp_wg_per_cu : kCUs * 4;   // 128-thread workgroups, 4 per CU (2 waves per SIMD); FP: by LDS / waves
+  int G = (resident + lv->B - 1) / lv->B;
+  const int want = fp ? pl->tiles : (pl->tiles + 1) / 2;      // one item per wave (FP: per workgroup) at least
+  if (G > want) G = want;
+  if (G < 1) G = 1;
+  pl->G = G;
+  pl->nbands = 1;
+  return true;
+}
+
+// Latency-bound launches (coarse levels, small batches): ba_gather128q_kernel -- 4x4-pixel items, the whole item one step,
+// ~4x shorter serial chain per item than a tile's 16 steps (gather128q.hip) -- while the launch has at most kQuadRounds items
+// per resident wave (2 workgroups x 4 waves per CU); beyond that the tile kernels' shared stencils win.
+// kDevForceQuadGather: at any size (parity tests, A/B); kDevNoQuadGather: off.
+inline bool choose_quad(const banet_level_t* lv, int kCUs, int Bsel, GatherPlan* pl) {
+  // (kDevForcePatchGather / kDevDirectGather force the patch / direct tile kernels)
+  if (!(pl->c128 && lv->dense && !(lv->flags & (kDevNoQuadGather | kDevForcePatchGather | kDevDirectGather)))) return false;
+  const int qxn = (lv->W + 3) / 4, qyn = (lv->H + 3) / 4;
+  const long long qitems = (long long)qxn * qyn * Bsel * npairs(lv);
+  // (multi-frame windows: every virtual window redoes the depth dot -- half the limit: cfg-3's 40x30 x 32 x 4 = 9600 items wins,
+  //  cfg-5's 80x60 x 8 x 7 = 16800 loses 329 vs 210 us, profiles/r04_run9_*)
+  const long long qlimit = (long long)kQuadRounds * kCUs * 8 / (npairs(lv) > 1 ? 2 : 1);
+  if (!(qitems <= qlimit || (lv->flags & kDevForceQuadGather))) return false;
+  const int VBq = lv->B * npairs(lv);
+  pl->quad = 1;
+  pl->tiles_x = qxn;
+  pl->tiles_y = qyn;
+  pl->tiles = qxn * qyn;
+  int G = (kCUs * 2 + VBq - 1) / VBq;            // one resident round of 256-thread workgroups, 2 per CU
+  const int want = (pl->tiles + kNumWaves - 1) / kNumWaves;
+  if (G > want) G = want;
+  if (G < 1) G = 1;
+  pl->G = G;
+  pl->nbands = 1;
+  return true;
+}
+
+// The 8x8-tile kernels -- patch, direct (C = 128) or generic -- take every launch the two above left.
+// One resident round: the gather is latency-bound per wave (measured: a second, partial round of
+// workgroups takes as long as the first), so the grid is what the chip holds at once, split
+// across the windows.
+inline void choose_tile(const banet_level_t* lv, int kCUs, int Bsel, GatherPlan* pl) {
+  // Large dense levels (>= 4 tiles per resident wave): ba_gather128p_kernel -- wave-private LDS patches with a
+  // software-pipelined box prefetch, 2 workgroups per CU (measured 640x480 x 8: 138 -> 125 us/window, 320x240 x 8:
+  // 48 -> 38); smaller levels are latency-bound and keep the 3-per-CU direct kernel.  kDevDirectGather: direct (A/B).
+  pl->patch = (pl->c128 && lv->dense && !(lv->flags & kDevDirectGather) &&
+               ((long long)pl->tiles * Bsel * npairs(lv) >= 4LL * kCUs * kPatchBlocksPerCU * kNumWaves ||
+                (lv->flags & kDevForcePatchGather))) ? 1 : 0;   // kDevForcePatchGather: at any size (parity tests)
+  const int resident = kCUs * (pl->patch ? kPatchBlocksPerCU : pl->c128 ? kC128BlocksPerCU : kGenericBlocksPerCU);
+  const int VB = lv->B * npairs(lv);   // virtual windows
+  const int VBsel = Bsel * npairs(lv);
+  // the generic kernel publishes one partial row per WORKGROUP (rows = G), so its grid is part of the arithmetic: taken from Bsel;
+  // the C = 128 kernels publish one row per work item in a fixed place, their grid is free to follow the launch
+  const int Bgrid = pl->c128 ? lv->B : Bsel;
+  // the patch kernel loops over a window's target frames inside a tile (depth dot once per window) where a window alone has
+  // >= 4 tiles per resident wave; below that the 4x coarser items cost more than the shared depth saves (80x60 x 32
+  // windows x 4 frames: 327 -> 478 us) and a work item stays one pair's tile
+  pl->pairloop = (pl->patch && npairs(lv) > 1 && ((long long)pl->tiles * Bsel >= 4LL * kCUs * kPatchBlocksPerCU * kNumWaves ||
+                                                   (lv->flags & kDevPatchPairLoop))) ? 1 : 0;   // kDevPatchPairLoop: force it (parity tests)
+  const int gy = pl->pairloop ? Bgrid : Bgrid * npairs(lv);
+  int target = (resident + gy - 1) / gy;
+  // Mid-size levels (a few tiles per wave at most) start all their waves in the same phase: measured, ~1300 waves
+  // finish a tile in 67 us but 2560 need 169 us (160x120 x 8: one tile per wave 21.1 us/window, two per wave on half
+  // the waves 16.7).  Such levels run on at most 320 workgroups (1280 waves).
+  if (pl->c128 && !pl->patch && (long long)pl->tiles * VBsel < 4LL * kCUs * kPatchBlocksPerCU * kNumWaves)
+    target = std::min(target, (320 + VB - 1) / VB);
+  // quarter-tile work items pay (measured: 40x30 x 8 windows 94 -> 50 us) only while they still leave the chip
+  // mostly empty -- at most one item per SIMD; beyond that the redone depth dot / geometry costs more than
+  // the shorter step chain saves (80x60 x 8: 101 -> 132 us).  kDevNoQuarterTiles: off (A/B).
+  pl->qshift = (pl->c128 && !pl->patch && pl->tiles <= 32 && (long long)pl->tiles * VBsel * 4 <= (long long)kCUs * 4 &&
+                !(lv->flags & kDevNoQuarterTiles)) ? 2 : 0;
+  if (pl->c128 && !pl->patch && (lv->flags & kDevQuarterTiles)) pl->qshift = 2;   // kDevQuarterTiles: force quarter tiles (A/B)   // (80x60 x 2 windows, also 640 items, LOSES 82 vs 51 us: coarsest levels only)
+  int G = pl->c128 ? ((pl->tiles << pl->qshift) + 3) / 4 : pl->groups;
+  if (G > target) {
+    G = target >= 8 ? (target & ~7) : target;   // several work items per wave: one resident round, no more
+  } else if (G >= 8) {
+    G = (G + 7) & ~7;   // every item gets its own wave in ONE round (rounding down left a few items for a second
+                        // pass: 2x the latency of a level that is pure latency); surplus workgroups find nothing and exit
+  }
+  if (G < 1) G = 1;
+  pl->G = G;
+  pl->nbands = (G & 7) == 0 ? 8 : 1;
+}
+
+// The partial region: [rows x row] [frows x row, when ba_fold_kernel runs] [tile-queue heads]; then the per-pixel records.
+// The C = 128 kernels write one row per work item, the generic kernel one per workgroup.
+inline void layout_partials(GatherPlan* pl, const banet_level_t* lv) {
+  const int VB = lv->B * npairs(lv);   // virtual windows
+  pl->pstride = kGHdr + lv->C;
+  pl->rows = pl->c128 ? (pl->tiles << pl->qshift) : pl->G;
+  pl->frows = pl->rows > kFoldRows ? (pl->rows + kFoldRows - 1) / kFoldRows : pl->rows;
+  const size_t row_bytes = (size_t)VB * pl->pstride * sizeof(float);
+  pl->off_fold = align_up(row_bytes * pl->rows, 256);
+  pl->off_queue = pl->off_fold + (pl->frows != pl->rows ? align_up(row_bytes * pl->frows, 256) : 0);
+  pl->partial_bytes = pl->off_queue + align_up((size_t)VB * 8 * sizeof(int), 256);
+  pl->rec_bytes = lv->K > 0 ? align_up((size_t)VB * lv->N * 8 * sizeof(float), 256) : 0;
+}
+
+}  // namespace plan_detail
+
+// kCUs: compute units of the part the launch is planned for (the .hip callers pass num_cus()).
+inline int plan_gather(const banet_level_t* lv, int kCUs, GatherPlan* pl) {
+  using namespace plan_detail;
+  *pl = GatherPlan{};
+  // 1. validate
+  if (!lv || lv->B <= 0 || lv->N <= 0 || lv->C <= 0 || lv->K < 0 || lv->H < 4 || lv->W < 4) return BANET_ERR_INVALID_ARG;
+  // (the field was a must-be-zero pad until round 4: anything but the two policies is a caller's garbage, not "throughput")
+  if (lv->policy != BANET_POLICY_THROUGHPUT && lv->policy != BANET_POLICY_BATCH_INVARIANT) return BANET_ERR_INVALID_ARG;
+  if (lv->C > 256 || lv->K > 256) return BANET_ERR_UNSUPPORTED;
+  if (lv->dense && lv->N != lv->H * lv->W) return BANET_ERR_INVALID_ARG;
+  const int Bsel = selection_batch(lv);   // decisions: Bsel; grids and buffer sizes: lv->B
+  // 2. tiling: 8x8-pixel tiles of a dense level, or runs of tile_pts sparse points
+  if (lv->dense) {
+    pl->tiles_x = (lv->W + 7) / 8;
+    pl->tiles_y = (lv->H + 7) / 8;
+    pl->tiles = pl->tiles_x * pl->tiles_y;
+    pl->tile_pts = kTilePix;
+  } else {
+    // Sparse points: 64 per wave item -- or 16 (round 6) while four times as many items still fit one resident round: the item is
+    // a serial chain of its points (the reference's own tracker, N = 4096 at batch 1: 64 items = 64 waves on 16 CUs, 54 us per launch)
+    // (chosen before c128 is known, though only ba_gather_kernel honours tile_pts -- kept as it is here)
+    const long long items64 = (long long)((lv->N + kTilePix - 1) / kTilePix) * Bsel * npairs(lv);
+    pl->tile_pts = (4 * items64 <= (long long)kCUs * kGenericBlocksPerCU * kNumWaves && !(lv->flags & kDevSparseItems64)) ? 16 : kTilePix;   // kDevSparseItems64: 64 (A/B)
+    pl->tiles = (lv->N + pl->tile_pts - 1) / pl->tile_pts;
+  }
+  pl->groups = (pl->tiles + 3) / 4;
+  pl->c128 = use_c128(lv) ? 1 : 0;
+  // 3. the kernel: the first candidate that takes the launch (each fills its own choices: work items, grid, bands)
+  if (!choose_strip(lv, kCUs, Bsel, pl) && !choose_quad(lv, kCUs, Bsel, pl)) choose_tile(lv, kCUs, Bsel, pl);
+  // 4. the partial buffer
+  layout_partials(pl, lv);
+  return BANET_OK;
+}
+
+// ---- syrk ------------------------------------------------------------------------------
+struct SyrkPlan {
+  int Gs, tiles, pstride, nb;
+  int x3;       // ba_syrk_bf16x6_kernel, opt-in: three products instead of six (kDevSyrkThreeProducts)
+  int direct;   // 0: the LDS-tiled kernel, 1: ba_syrk_direct_kernel (fp32 MFMA, A/B), 2: ba_syrk_bf16x6_kernel (K = 64 / 128, <= 4 frames),
+                // 3: syrk_wide.hip jobs (K = 256, or K = 128 with more than 4 target frames)
+  int f16;      // ba_syrk_bf16x6_kernel: the fp16 two-piece form is eligible (plan_syrk); f16_standalone: also in a single assembly pass
+  int f16_standalone;
+  size_t off_colmax, off_recmax;   // f16: [B][K] basis column maxima, [B][32][2] record maxima, inside the partial buffer
+  size_t off_aux;        // direct == 3: per-pixel (s, r) sums over the frames, inside the partial buffer
+  size_t partial_bytes;
+};
+
+constexpr long long kSyrkF16Pixels = 32LL * 76800;   // 320x240 x 32 windows, 640x480 x 8
+inline size_t syrk_wide_aux_bytes(int B, int N, int pairs) { return pairs > 1 ? align_up((size_t)B * N * 2 * sizeof(float), 256) : 0; }
+
+inline int nb_for_k(int K) {   // 16-column blocks of the LDS-tiled kernel
+  if (K <= 0) return 0;
+  if (K <= 16) return 1;
+  if (K <= 32) return 2;
+  if (K <= 64) return 4;
+  if (K <= 128) return 8;
+  if (K <= 256) return 16;
+  return -1;
+}
+
+// Bsel: the batch the decisions are taken from (selection_batch); flags: banet_level_t.flags; cus: as plan_gather's kCUs
+inline int plan_syrk(int B, int Bsel, int N, int K, int pairs, int flags, int cus, SyrkPlan* pl) {
+  *pl = SyrkPlan{};
+  pl->nb = nb_for_k(K);
+  if (pl->nb < 0) return BANET_ERR_UNSUPPORTED;
+  if (K == 0) return BANET_OK;   // no depth block: nothing runs
+  pl->tiles = (N + kTilePix - 1) / kTilePix;
+  // K = 64 / 128: barrier-free kernels, one wave per SIMD, one workgroup per CU in all: 2 = ba_syrk_bf16x6_kernel
+  // (default), 1 = ba_syrk_direct_kernel (fp32 MFMA; kDevSyrkNoBf16x6, A/B only)
+  pl->direct = ((K == 64 || K == 128) && pairs <= 4) ? ((flags & kDevSyrkNoBf16x6) ? 1 : 2) : 0;
+  // OPT-IN (kDevSyrkThreeProducts, K = 128): the three largest of the six products only -- a two-piece split, 16 significand bits per
+  // operand, ~2^-16 relative error per product instead of 2^-24.  Not the product path and not what bench.py's `value` is measured
+  // with (its dtype is "f32": fp32-exact products); measured beside it: profiles/r03_run31_*, DESIGN.md section 7.
+  pl->x3 = (pl->direct == 2 && K == 128 && (flags & kDevSyrkThreeProducts)) ? 1 : 0;
+  // K = 256, or K = 128 with more than 4 target frames: the job kernels of syrk_wide.hip (kDevSyrkNoBf16x6: the LDS-tiled kernel, A/B)
+  if (!(flags & kDevSyrkNoBf16x6) && (K == 256 || (K == 128 && pairs > 4))) pl->direct = 3;
+  int target = (((pl->direct || pl->nb > 8) ? cus : 2 * cus) + Bsel - 1) / Bsel;   // Gs = partial rows per window: part of the arithmetic, hence from Bsel   // LDS kernel: 2 resident workgroups per CU (1 at K > 128)
+  int G = pl->direct ? (N + 4 * 4 * 16 - 1) / (4 * 4 * 16) : pl->tiles / 4;   // direct: >= 16 quads per wave
+  if (G > target) G = target;
+  if (G < 1) G = 1;
+  pl->Gs = G;
+  pl->pstride = (int)align_up((size_t)(6 * pairs + 1) * K + (size_t)K * K, 4);
+  pl->partial_bytes = align_up((size_t)B * G * pl->pstride * sizeof(float), 256);
+  pl->off_aux = pl->partial_bytes;
+  if (pl->direct == 3) pl->partial_bytes += syrk_wide_aux_bytes(B, N, pairs);
+  // The fp16 two-piece form of ba_syrk_bf16x6_kernel (half the MFMAs, 5 instead of 9 split instructions per two values, the same
+  // accuracy class: ~2^-21 per product against the reference's fp32 GEMM) where the launch is throughput-bound -- at least
+  // kSyrkF16Pixels pixels in all -- so that its two small pre-passes (basis column maxima once per level, record maxima per pass)
+  // are noise.  LM loop (banet_lm_level_f32) only; the single assembly pass keeps the exact bf16 form unless kDevSyrkF16 asks
+  // for this one (tests).  kDevNoSyrkF16: never (A/B).
+  pl->f16 = ((pl->direct == 2 || pl->direct == 3) && !pl->x3 && !(flags & kDevNoSyrkF16) && ((long long)N * Bsel >= kSyrkF16Pixels || (flags & kDevSyrkF16))) ? 1 : 0;
+  pl->f16_standalone = (pl->f16 && (flags & kDevSyrkF16)) ? 1 : 0;
+  pl->off_colmax = pl->partial_bytes;
+  pl->off_recmax = pl->off_colmax + (pl->f16 ? align_up((size_t)B * K * sizeof(float), 256) : 0);
+  if (pl->f16) pl->partial_bytes = pl->off_recmax + align_up((size_t)B * kRecMaxBlocks * 2 * sizeof(float), 256);
+  return BANET_OK;
+}
+
+// ---- one assembly pass = gather + syrk + reduce -----------------------------------------
+struct AsmPlan {
+  GatherPlan g;
+  SyrkPlan s;
+  int P;
+  size_t ws_bytes;      // gather partials + records + syrk partials
+  size_t off_rec, off_spart;
+};
+
+inline int plan_assemble(const banet_level_t* lv, int cus, AsmPlan* pl) {
+  *pl = AsmPlan{};
+  int rc = plan_gather(lv, cus, &pl->g);
+  if (rc != BANET_OK) return rc;
+  rc = plan_syrk(lv->B, selection_batch(lv), lv->N, lv->K, npairs(lv), lv->flags, cus, &pl->s);
+  if (rc != BANET_OK) return rc;
+  pl->P = 6 * npairs(lv) + lv->K;
+  pl->off_rec = pl->g.partial_bytes;
+  pl->off_spart = pl->off_rec + pl->g.rec_bytes;
+  pl->ws_bytes = pl->off_spart + pl->s.partial_bytes;
+  return BANET_OK;
+}
+
+}  // namespace banet

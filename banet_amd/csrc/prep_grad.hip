@@ -324,19 +324,14 @@ void rg_plan(int B, int N, int H, int W, RgPlan* pl) {
   int bits = 1;
   while ((pl->ncells >> bits) != 0) ++bits;     // keys 0 .. ncells (the unsampled sentinel)
   pl->passes = (bits + 7) / 8;
-  size_t o = 0;
-  auto take = [&](size_t nb) {
-    const size_t at = o;
-    o = align_up(o + nb, 256);
-    return at;
-  };
-  pl->off_k0 = take((size_t)B * N * 4);
-  pl->off_v0 = take((size_t)B * N * 4);
-  pl->off_k1 = take((size_t)B * N * 4);
-  pl->off_v1 = take((size_t)B * N * 4);
-  pl->off_hist = take((size_t)B * 256 * pl->ntiles * 4);
-  pl->off_cs = take((size_t)B * pl->ncells * 8);
-  pl->bytes = o;
+  Arena ar;
+  pl->off_k0 = ar.take((size_t)B * N * 4);
+  pl->off_v0 = ar.take((size_t)B * N * 4);
+  pl->off_k1 = ar.take((size_t)B * N * 4);
+  pl->off_v1 = ar.take((size_t)B * N * 4);
+  pl->off_hist = ar.take((size_t)B * 256 * pl->ntiles * 4);
+  pl->off_cs = ar.take((size_t)B * pl->ncells * 8);
+  pl->bytes = ar.off;
 }
 
 int dog_blocks(int N) { return std::max(1, std::min(256, (N + 255) / 256)); }

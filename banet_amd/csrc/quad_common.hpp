@@ -112,7 +112,7 @@ __device__ __forceinline__ float quad_bcast(float v) {
 struct SGeo {
   float dx, dy, jd0, jd1;
   float jc[12];
-  int x0, y0, flags;   // flags: 1 = in the mask, 2 = fast (stencil inside the image), 4 = in the mask but on the rim
+  int x0, y0, flags;   // kPix* bits (gather_common.hpp)
 };
 
 // the pixel's projection, tap fractions and Jacobian rows from (pixel, D, R, T): statement for statement the geometry
@@ -194,7 +194,7 @@ __device__ __forceinline__ void strip_geometry(const banet_level_t& lv, const Po
   }
   const bool interior = (x0 >= 1) && (x0 + 2 <= W - 1) && (y0 >= 1) && (y0 + 2 <= H - 1);
   const bool fast = m && interior;
-  o.flags = (m ? 1 : 0) | (fast ? 2 : 0) | ((m && !fast) ? 4 : 0);
+  o.flags = (m ? kPixInMask : 0) | (fast ? kPixFast : 0) | ((m && !fast) ? kPixRim : 0);
   o.x0 = x0;
   o.y0 = y0;
 }

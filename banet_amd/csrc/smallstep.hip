@@ -352,19 +352,14 @@ struct SsPlan {
   size_t off_Ad, off_rhs, off_ladj, off_scal, off_act, off_dlt, bytes;
 };
 void ss_plan(int B, int C, int P, SsPlan* pl) {
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  pl->off_Ad = take((size_t)B * P * P * 4);
-  pl->off_rhs = take((size_t)B * P * 4);
-  pl->off_ladj = take((size_t)B * P * 4);
-  pl->off_scal = take((size_t)B * 4 * 4);
-  pl->off_act = take((size_t)B * ss_act_floats(C) * 4);
-  pl->off_dlt = take((size_t)B * ss_act_floats(C) * 4);
-  pl->bytes = o;
+  Arena ar;
+  pl->off_Ad = ar.take((size_t)B * P * P * 4);
+  pl->off_rhs = ar.take((size_t)B * P * 4);
+  pl->off_ladj = ar.take((size_t)B * P * 4);
+  pl->off_scal = ar.take((size_t)B * 4 * 4);
+  pl->off_act = ar.take((size_t)B * ss_act_floats(C) * 4);
+  pl->off_dlt = ar.take((size_t)B * ss_act_floats(C) * 4);
+  pl->bytes = ar.off;
 }
 
 }  // namespace

@@ -499,7 +499,6 @@ static void launch_slice(const WideArgs& a, int B, int pt, hipStream_t s) {
   }
 }
 
-size_t syrk_wide_aux_bytes(int B, int N, int pairs) { return pairs > 1 ? align_up((size_t)B * N * 2 * sizeof(float), 256) : 0; }
 
 int launch_syrk_wide(const float* basis, const float* rec, int B, int N, int K, int pairs, int Gs, int pstride,
                      const int32_t* active, int active_stride, float* partials, float* aux, hipStream_t s, const float* colmax,

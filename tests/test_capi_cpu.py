@@ -428,9 +428,9 @@ def test_kernel_selection_table_of_the_baseline_configs(capi):
     assert sel(1, 120, 160, 32, 1) == (4, 0)
     # the documented development bits
     h, w = pyr[0]
-    assert sel(32, h, w, 128, 1, reserved=1 << 30)[0] == 1 and sel(32, 480, 640, 128, 1, reserved=-2147483648)[1] == 2
-    assert sel(32, h, w, 128, 1, reserved=(1 << 18) | 1024)[0] == 3
-    assert sel(6, 240, 320, 128, 1)[0] == 1 and sel(6, 240, 320, 128, 1, reserved=1 << 25)[0] == 4      # (28800 items: beyond its limit -> tiles)
+    assert sel(32, h, w, 128, 1, reserved=capi.DEV_NO_QUAD_GATHER)[0] == 1 and sel(32, 480, 640, 128, 1, reserved=capi.DEV_NO_SYRK_F16)[1] == 2
+    assert sel(32, h, w, 128, 1, reserved=capi.DEV_FORCE_STRIP_GATHER | capi.DEV_QUARTER_TILES)[0] == 3
+    assert sel(6, 240, 320, 128, 1)[0] == 1 and sel(6, 240, 320, 128, 1, reserved=capi.DEV_FORCE_QUAD_GATHER)[0] == 4      # (28800 items: beyond its limit -> tiles)
 
 
 def test_batch_invariant_policy_selects_by_level_only(capi):
@@ -455,8 +455,8 @@ def test_batch_invariant_policy_selects_by_level_only(capi):
     lv.policy = 1
     assert L.banet_lm_level_workspace_bytes(ctypes.byref(lv)) > 0 and L.banet_gather_selection(ctypes.byref(lv)) > 0
     # the old field name is an alias of the new one (tools/ still use it)
-    lv.reserved_ = 1 << 18
-    assert lv.flags == 1 << 18
+    lv.reserved_ = capi.DEV_FORCE_STRIP_GATHER
+    assert lv.flags == capi.DEV_FORCE_STRIP_GATHER
 
 
 def test_adjoint_accepts_the_sparse_reference_layout(capi):

@@ -500,13 +500,14 @@ def test_patch_gather_kernel_matches_oracle(H, W, K, big, pairs):
     mlps = [orc.he_normal_mlp_weights(C, 9)]
     ba = bdense.DenseBA(t(intr), _torch_levels(levels), mlps, "bundle" if K else "bundle_camera", 1000.0)
     outs = {}
-    for bits in (512, 64, 512 | 4096):                           # patch kernel forced / direct kernel / patch kernel with the
+    PATCH, DIRECT, PATCH_LOOP = ops.capi.DEV_FORCE_PATCH_GATHER, ops.capi.DEV_DIRECT_GATHER, ops.capi.DEV_FORCE_PATCH_GATHER | ops.capi.DEV_PATCH_PAIR_LOOP
+    for bits in (PATCH, DIRECT, PATCH_LOOP):                           # patch kernel forced / direct kernel / patch kernel with the
         ba.problems[0].c.flags = bits                         # target frames looped over inside a tile (large levels)
         outs[bits] = [n(x) for x in ops.ba_assemble(ba.problems[0], t(R), t(T), t(Wc) if K else None)]
     ba.problems[0].c.flags = 0
-    for x, y in zip(outs[512], outs[64]):
+    for x, y in zip(outs[PATCH], outs[DIRECT]):
         assert relerr(x, y) < 2e-6, relerr(x, y)
-    for x, y in zip(outs[512 | 4096], outs[512]):                 # same arithmetic per pair: identical bits
+    for x, y in zip(outs[PATCH_LOOP], outs[PATCH]):                 # same arithmetic per pair: identical bits
         np.testing.assert_array_equal(x, y)
     one = dict(lv)
     one["tgt"] = lv["tgt"][:, 0]
@@ -517,16 +518,16 @@ def test_patch_gather_kernel_matches_oracle(H, W, K, big, pairs):
         conv2s = [orc.target_map(lv["tgt"][:, i].astype(np.float64)) for i in range(pairs)]
         dbg = orc.bundle_window_iteration(a["conv1"], conv2s, a["fx"], a["fy"], a["ox"], a["oy"], a["p"], a["D"], a["Bs"],
                                           R64, T64, Wc.astype(np.float64), mlps[0], 1000.0)[3]
-        assert relerr(outs[512][0], dbg["AtA"]) < 3e-5 and relerr(outs[512][1][..., None], dbg["Atb"]) < 3e-5
+        assert relerr(outs[PATCH][0], dbg["AtA"]) < 3e-5 and relerr(outs[PATCH][1][..., None], dbg["Atb"]) < 3e-5
         nv = sum(m.sum(axis=(1, 2)) for m in dbg["mask"])
-        assert np.abs(outs[512][3] - nv).max() <= 1
+        assert np.abs(outs[PATCH][3] - nv).max() <= 1
         if big:
             assert (nv < H * W * pairs).all()                     # some pixels really leave the image
     else:
         for i in range(pairs):
             d = orc.bundle_camera_iteration(a["conv1"], orc.target_map(lv["tgt"][:, i].astype(np.float64)), a["fx"], a["fy"],
                                             a["ox"], a["oy"], a["p"], a["D"], R64[i], T64[i], mlps[0], 1.0)[2]
-            assert relerr(outs[512][0][:, 6 * i:6 * i + 6, 6 * i:6 * i + 6], d["AtA"]) < 3e-5
+            assert relerr(outs[PATCH][0][:, 6 * i:6 * i + 6, 6 * i:6 * i + 6], d["AtA"]) < 3e-5
 
 
 @pytest.mark.parametrize("C,K,pairs", [(128, 256, 7), (12, 200, 2), (128, 256, 1), (128, 128, 6), (20, 256, 5)])

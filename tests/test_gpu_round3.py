@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import cases
+from banet_amd import _capi as F     # the DEV_* names of banet_level_t.flags
 from oracle import banet_oracle as orc, torch_port
 
 pytestmark = pytest.mark.gpu
@@ -220,9 +221,10 @@ def _torch_levels(levels):
                               t(lv["basis"]) if lv["basis"].shape[-1] else None) for lv in levels]
 
 
-STRIP, DIRECT, STRIP_ALL_DIRECT, SEG32 = 262144, 64 | 524288, 262144 | (1 << 20), 1 << 21
-PAIR_LOOP = 1 << 22      # multi-frame strip gather: frames looped over inside one wave (A/B)
-SEG8 = 1024              # with STRIP: 8-row segments (mid-size two-frame launches)
+STRIP, DIRECT, STRIP_ALL_DIRECT, SEG32 = (F.DEV_FORCE_STRIP_GATHER, F.DEV_DIRECT_GATHER | F.DEV_NO_STRIP_GATHER,
+                                          F.DEV_FORCE_STRIP_GATHER | F.DEV_STRIP_DIRECT_ROWS, F.DEV_STRIP_ROWS32)
+PAIR_LOOP = F.DEV_STRIP_FRAME_LOOP      # multi-frame strip gather: frames looped over inside one wave (A/B)
+SEG8 = F.DEV_QUARTER_TILES              # with STRIP: 8-row segments (mid-size two-frame launches)
 
 
 @pytest.mark.parametrize("H,W,K,big,pairs", [(48, 64, 128, False, 1),      # whole segments, unit-scale footprints: all from the window
@@ -351,7 +353,7 @@ def test_cg_solve_and_ldlt_fallback_match_the_oracle_lu(l2_base, pairs):
     ba = bdense.DenseBA(t(intr), _torch_levels(levels), mlps, "bundle", l2_base)
     AtA, Atb, absres, nvalid = ops.ba_assemble(ba.problems[0], t(R), t(T), t(Wc))
     sols = {}
-    for bits in (0, 1 << 23):
+    for bits in (0, F.DEV_SOLVE_LDLT_ONLY):
         ba.problems[0].c.flags = bits
         st = ba.new_state(t(R.reshape(B * pairs, 3, 3)), t(T.reshape(B * pairs, 3, 1)), t(Wc))
         ops.ba_solve_update(ba.problems[0], ba.mlps[0], l2_base, AtA, Atb, absres, nvalid, st)
@@ -371,7 +373,7 @@ def test_cg_solve_and_ldlt_fallback_match_the_oracle_lu(l2_base, pairs):
                 assert err < 1e-4, (l2_base, pairs, b, name, bits, err, lam)
     # (both are within 1e-4 of the float64 solution per group; against each other: 5e-5 of the largest entry -- the weakly damped
     # cases, l2_base <= 1, are conditioned ~1e3 and sit at 2-3e-5 depending on the rounding of the assembled matrix)
-    assert np.abs(sols[0][0] - sols[1 << 23][0]).max() <= 5e-5 * np.abs(sols[1 << 23][0]).max()
+    assert np.abs(sols[0][0] - sols[F.DEV_SOLVE_LDLT_ONLY][0]).max() <= 5e-5 * np.abs(sols[F.DEV_SOLVE_LDLT_ONLY][0]).max()
 
 
 def test_strip_gather_under_the_legacy_early_terminated_lm():

@@ -10,13 +10,15 @@ import numpy as np
 import pytest
 import torch
 
+from banet_amd import _capi as F     # the DEV_* names of banet_level_t.flags
 from oracle import banet_oracle as orc, torch_port
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-GENERIC, DIRECT, PATCH, STRIP, STRIP_PAIR_LOOP = 32 | (1 << 30), 64 | 524288 | (1 << 30), 512 | (1 << 30), 262144, 262144 | (1 << 22)
-QUAD = 1 << 25
+GENERIC, DIRECT, PATCH = (F.DEV_GENERIC_GATHER | F.DEV_NO_QUAD_GATHER, F.DEV_DIRECT_GATHER | F.DEV_NO_STRIP_GATHER | F.DEV_NO_QUAD_GATHER,
+                          F.DEV_FORCE_PATCH_GATHER | F.DEV_NO_QUAD_GATHER)
+STRIP, STRIP_PAIR_LOOP, QUAD = F.DEV_FORCE_STRIP_GATHER, F.DEV_FORCE_STRIP_GATHER | F.DEV_STRIP_FRAME_LOOP, F.DEV_FORCE_QUAD_GATHER
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -175,7 +177,7 @@ def test_twin_with_forced_mask():
 # ======================================================================================
 # the fp16 two-piece form of the depth-block contraction (syrk.hip, ba_syrk_bf16x6_kernel<.., .., 16>)
 # ======================================================================================
-SYRK_F16 = 1 << 24          # the single assembly pass runs it too (default: LM loop, throughput-bound launches only)
+SYRK_F16 = F.DEV_SYRK_F16          # the single assembly pass runs it too (default: LM loop, throughput-bound launches only)
 
 
 def _entry_errors(AtA, Atb, absres, A64, b64):
@@ -282,7 +284,7 @@ def test_lm_loop_with_the_f16_syrk_matches_the_exact_form_and_the_twin():
     ba = bdense.DenseBA(intr, levels, mlps, "bundle", 1000.0)
     T0 = (gt["T"] * 0.7).reshape(B, 3, 1).to(DEV)
     res = {}
-    for bits in (SYRK_F16, -2147483648):
+    for bits in (SYRK_F16, F.DEV_NO_SYRK_F16):
         for prob in ba.problems:
             prob.c.flags = bits
         st, counts = ba.solve([10, 10], ba.new_state(T=T0.clone()))
@@ -291,7 +293,7 @@ def test_lm_loop_with_the_f16_syrk_matches_the_exact_form_and_the_twin():
         res[bits] += (s1.delta.clone(), s1.lambda_out.clone())
     for prob in ba.problems:
         prob.c.flags = 0
-    a, e = res[SYRK_F16], res[-2147483648]
+    a, e = res[SYRK_F16], res[F.DEV_NO_SYRK_F16]
 
     def rel(x, y):
         return float((x - y).abs().max() / y.abs().max())

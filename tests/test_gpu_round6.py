@@ -270,7 +270,7 @@ def test_solve_differentiable_with_the_hip_small_step_equals_the_torch_small_ste
 @pytest.mark.parametrize("B,N,C,K", [(1, 4096, 128, 0), (2, 1000, 70, 33), (3, 777, 128, 128)])
 def test_sparse_gather_with_16_point_items_equals_the_64_point_items(B, N, C, K):
     """ba_gather_kernel on sparse points (the reference's tracker / training layout): latency-bound launches cut the wave items to 16
-    points (round 6: 4x the waves, the reference's own N = 4096 batch-1 tracker 2.06 -> 1.35 ms per solve); flags bit 1 keeps 64.
+    points (round 6: 4x the waves, the reference's own N = 4096 batch-1 tracker 2.06 -> 1.35 ms per solve); DEV_SPARSE_ITEMS64 keeps 64.
     Same sums to rounding (another grouping of the partial rows), the in-image counts exactly; ragged N (a last item with empty slots)."""
     from banet_amd import ops
     g = torch.Generator().manual_seed(B * 1000 + N)
@@ -289,7 +289,7 @@ def test_sparse_gather_with_16_point_items_equals_the_64_point_items(B, N, C, K)
     T = (0.02 * torch.randn(B, 3, 1, generator=g)).to(DEV)
     Wc = (0.01 * torch.randn(B, K, 1, generator=g)).to(DEV) if K else None
     outs = {}
-    for bits in (0, 2):
+    for bits in (0, ops.capi.DEV_SPARSE_ITEMS64):
         prob = ops.LevelProblem("bundle" if K else "bundle_camera", conv1, conv2, D, H, W, C, basis=Bs, rays=p, fx=fx, fy=fx.clone(), ox=ox, oy=oy,
                                 dense=False, tgt_has_grad=True)
         prob.c.flags = bits

@@ -17,14 +17,16 @@ import pytest
 import torch
 
 import ws_contract as wsc
+from banet_amd import _capi as F     # the DEV_* names of banet_level_t.flags
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 # development bits of banet_level_t.flags that force a kernel (test_gpu_round4.py)
-GENERIC, DIRECT, PATCH, STRIP, STRIP_PAIR_LOOP = 32 | (1 << 30), 64 | 524288 | (1 << 30), 512 | (1 << 30), 262144, 262144 | (1 << 22)
-QUAD = 1 << 25
-SYRK_F16, SYRK_FP32_OR_LDS, MLP_IN_SOLVE = 1 << 24, 256, 32768
+GENERIC, DIRECT, PATCH = (F.DEV_GENERIC_GATHER | F.DEV_NO_QUAD_GATHER, F.DEV_DIRECT_GATHER | F.DEV_NO_STRIP_GATHER | F.DEV_NO_QUAD_GATHER,
+                          F.DEV_FORCE_PATCH_GATHER | F.DEV_NO_QUAD_GATHER)
+STRIP, STRIP_PAIR_LOOP, QUAD = F.DEV_FORCE_STRIP_GATHER, F.DEV_FORCE_STRIP_GATHER | F.DEV_STRIP_FRAME_LOOP, F.DEV_FORCE_QUAD_GATHER
+SYRK_F16, SYRK_FP32_OR_LDS, MLP_IN_SOLVE = F.DEV_SYRK_F16, F.DEV_SYRK_NO_BF16X6, F.DEV_MLP_IN_SOLVE
 GATHER_OF = {GENERIC: 0, DIRECT: 1, PATCH: 2, STRIP: 3, STRIP_PAIR_LOOP: 3, QUAD: 4}
 
 _ARENA = []
@@ -204,7 +206,7 @@ def test_ba_assemble_on_sparse_points(B, N, C, K):
     R = torch.eye(3, device=DEV).repeat(B, 1, 1)
     T = (0.02 * torch.randn(B, 3, 1, generator=g)).to(DEV)
     Wc = (0.01 * torch.randn(B, K, 1, generator=g)).to(DEV) if K else None
-    for bits in (0, 2):                                   # 16-point items where the launch is latency-bound / always 64
+    for bits in (0, F.DEV_SPARSE_ITEMS64):                              # 16-point items where the launch is latency-bound / always 64
         def run():
             prob = ops.LevelProblem("bundle" if K else "bundle_camera", conv1, conv2, D, H, W, C, basis=Bs, rays=p, fx=fx, fy=fx.clone(),
                                     ox=ox, oy=oy, dense=False, tgt_has_grad=True)

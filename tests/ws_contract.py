@@ -228,7 +228,7 @@ def abi_cases(capi):
         mlp.w[i] = mlp.b[i] = pv
     keep = []
     for B, H, W, K, pairs, policy in levels:
-        for flags in (0, 1 << 24):                     # default selection; the fp16 two-piece SYRK where it applies (colmax / recmax regions)
+        for flags in (0, capi.DEV_SYRK_F16):                   # default selection; the fp16 two-piece SYRK where it applies (colmax / recmax regions)
             if flags and K not in (128, 256):
                 continue
             lv = _abi_level(capi, pv, B, H, W, K, pairs, policy=policy, flags=flags)

@@ -96,6 +96,22 @@ class LmParams(ctypes.Structure):
 
 SOLVER_QR, SOLVER_INVERSE = 0, 1
 
+
+class SolveTrace(ctypes.Structure):
+    """mirror of banet_solve_trace_t: the state after every level, [n_levels][B]... rows (every pointer optional); `depth` is a
+    host array of n_levels device pointers"""
+    _fields_ = [("R", _FP), ("T", _FP), ("Wc", _FP), ("lambda_out", _FP), ("delta", _FP), ("ratio", _FP), ("iters", _FP),
+                ("depth", ctypes.POINTER(_FP))]
+
+
+class Schedule(ctypes.Structure):
+    """mirror of banet_schedule_t (banet_lm_solve_f32: all levels of a solve in one call)"""
+    _fields_ = [("levels", ctypes.POINTER(Level)), ("n_levels", ctypes.c_int32), ("early_termination", ctypes.c_int32),
+                ("mlps", ctypes.POINTER(ctypes.POINTER(Mlp))), ("max_iters", ctypes.POINTER(ctypes.c_int32)),
+                ("l2_base", ctypes.c_float), ("params", ctypes.POINTER(LmParams)), ("workspace", _FP),
+                ("workspace_bytes", ctypes.c_size_t), ("trace", ctypes.POINTER(SolveTrace))]
+
+
 EXPORTS = {
     "banet_version": (ctypes.c_int, []),
     "banet_error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -128,6 +144,8 @@ EXPORTS = {
     "banet_lm_level_ex_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float, ctypes.c_int,
                                              ctypes.c_int, ctypes.POINTER(LmParams), ctypes.POINTER(State), _FP,
                                              ctypes.c_size_t, _FP]),
+    "banet_lm_solve_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Schedule)]),
+    "banet_lm_solve_f32": (ctypes.c_int, [ctypes.POINTER(Schedule), ctypes.POINTER(State), _FP]),
     "banet_sample_stats_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "banet_sample_stats_grad_det_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 5 + [_FP] * 5 + [_FP, ctypes.c_size_t, _FP]),
     "banet_spd_solve_f32": (ctypes.c_int, [_FP] * 3 + [ctypes.c_int] * 2 + [_FP]),

@@ -21,18 +21,7 @@ static int check_level(const banet_level_t* lv) {
   return BANET_OK;
 }
 
-struct LevelWs {  // carve of the level workspace
-  float* partials;
-  float* AtA;
-  float* Atb;
-  float* absres;
-  float* nvalid;
-  LmCtl* ctl;
-  float* mlp_y;   // [B] lambda-MLP outputs of the SYRK launch's role workgroups
-  float* bigA;
-  size_t total;
-};
-
+// (LevelWs: kernels.hpp)
 static LevelWs carve_level(const banet_level_t* lv, const AsmPlan& pl, void* ws) {
   LevelWs w;
   char* p = static_cast<char*>(ws);
@@ -92,6 +81,109 @@ static int check_state(const banet_level_t* lv, const banet_mlp_t* mlp, const ba
     if (!mlp) return BANET_ERR_INVALID_ARG;
     for (int i = 0; i < 5; ++i)
       if (!mlp->w[i] || !mlp->b[i]) return BANET_ERR_INVALID_ARG;
+  }
+  return BANET_OK;
+}
+
+
+constexpr int kRoleSmallLevel = 19200;   // pixels: levels whose SYRK launch is latency-bound (see the role condition below)
+
+int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, int early_termination,
+                  const banet_lm_params_t* params, const banet_state_t* st, void* ws, size_t ws_bytes, LevelRun* run) {
+  int rc = check_level(lv);
+  if (rc != BANET_OK) return rc;
+  rc = check_state(lv, mlp, st);
+  if (rc != BANET_OK) return rc;
+  if (max_iters < 0) return BANET_ERR_INVALID_ARG;
+  AsmPlan& pl = run->pl;
+  rc = plan_assemble(lv, num_cus(), &pl);
+  if (rc != BANET_OK) return rc;
+  if (!ws || !aligned256(ws)) return BANET_ERR_WORKSPACE;
+  LevelWs& w = run->w;
+  w = carve_level(lv, pl, ws);
+  if (ws_bytes < w.total) return BANET_ERR_WORKSPACE;
+  SolveArgs& a = run->a;
+  a = make_solve_args(lv, mlp, l2_base, w.AtA, w.Atb, w.absres, w.nvalid, st);
+  a.max_iters = max_iters;
+  a.bigA = w.bigA;
+  if (params) {
+    if (params->solver != BANET_SOLVER_QR && params->solver != BANET_SOLVER_INVERSE) return BANET_ERR_INVALID_ARG;
+    if (!(params->angle_change >= 0.f) || !(params->translation_change >= 0.f) || !(params->residual_ratio > 0.f))
+      return BANET_ERR_INVALID_ARG;   // also rejects NaN
+    a.lm = *params;
+  }
+  run->lv = lv;
+  run->mlp = mlp;
+  run->max_iters = max_iters;
+  run->lm = early_termination && lv->variant == BANET_LEGACY_LM;
+  run->role = false;
+  if (run->lm) {
+    a.ctl = w.ctl;
+  } else {
+    // the tile queue is reset once per level; afterwards every solve kernel leaves it zeroed for the next gather
+    a.queue = assemble_queue(pl, w.partials);
+    a.nqueue = 8 * npairs(lv);
+    // bundle levels whose SYRK is ba_syrk_bf16x6_kernel: the lambda MLP runs as a role workgroup of the SYRK launch, off the
+    // solve kernel's critical path (C <= 256: the role's LDS scratch)
+    // ... and coarse levels at any batch (N <= kRoleSmallLevel pixels: their SYRK is a latency chain of 1-3 steps per wave, so a
+    // window's 7 workgroups take what 8 take, and the solve kernel loses the 19 us MLP: 40x30 .. 160x120 x 32 windows).
+    // Small batches only (B <= 8) otherwise: the SYRK kernel runs one workgroup per CU (512 registers per wave), so the role workgroups
+    // need CUs of their own -- at B = 32 (8 + 1 workgroups per window = 288 > 256 CUs) a second round of workgroups doubled
+    // the SYRK time (640x480 x 32: 1326 -> 2457 us); with B <= 8 one SYRK workgroup per window is given up where needed.
+    const int Bsel = selection_batch(lv);   // (the role changes Gs, i.e. the summation split: decided like every other selection)
+    run->role = lv->variant == BANET_BUNDLE && mlp != nullptr && a.use_mlp && syrk_runs_mlp_role(pl.s) && lv->C <= 256 &&
+                (lv->C & 3) == 0 && ((long long)Bsel * (pl.s.Gs + 1) <= num_cus() || (Bsel <= 8 && pl.s.Gs >= 16) ||
+                 (lv->N <= kRoleSmallLevel && pl.s.Gs >= 4)) &&
+                !(lv->flags & kDevMlpInSolve);   // MLP inside the solve kernel (A/B)
+    if (run->role) {
+      a.mlp_y = w.mlp_y;
+      if ((long long)Bsel * (pl.s.Gs + 1) > num_cus()) pl.s.Gs -= 1;
+    }
+  }
+  return BANET_OK;
+}
+
+int lm_level_enqueue(const LevelRun& run, hipStream_t s) {
+  const banet_level_t* lv = run.lv;
+  const AsmPlan& pl = run.pl;
+  const LevelWs& w = run.w;
+  const SolveArgs& a = run.a;
+  const banet_state_t* st = &a.st;
+  const int max_iters = run.max_iters;
+  int rc;
+  if (run.lm) {
+    // device-side loop control: max_iters + 1 evaluation rounds; the last one only runs the
+    // pending accept/reject test (legacy/ba.py:304-345), see solve.hip
+    launch_ctl_init(w.ctl, st->iters, lv->B, s);
+    const int stride = (int)(sizeof(LmCtl) / sizeof(int32_t));
+    for (int it = 0; it <= max_iters; ++it) {
+      rc = launch_assemble(lv, pl, st->R, st->T, st->Wc, &w.ctl->active, stride, w.partials, w.AtA, w.Atb, w.absres,
+                           w.nvalid, s);
+      if (rc != BANET_OK) return rc;
+      {
+        RangeScope r("solve", lv->N);
+        rc = launch_solve(a, s);
+      }
+      if (rc != BANET_OK) return rc;
+    }
+  } else {
+    launch_zero_iters(st->iters, lv->B, s);
+    if (a.queue) launch_zero_iters(a.queue, lv->B * a.nqueue, s);   // a kernel, not hipMemsetAsync: see prepare_gather
+    const bool role = run.role;
+    const banet_mlp_t* mlp = run.mlp;
+    for (int it = 0; it < max_iters; ++it) {
+      rc = launch_assemble(lv, pl, st->R, st->T, st->Wc, nullptr, 0, w.partials, w.AtA, w.Atb, w.absres, w.nvalid, s,
+                           a.queue == nullptr, role ? mlp : nullptr, role ? w.mlp_y : nullptr, nullptr,
+                           // fp16 two-piece SYRK: the level's first pass runs the exact form and leaves the basis column maxima
+                           // on the way (no extra pass over the basis); a one-iteration call computes them up front instead
+                           pl.s.f16 ? (it == 0 ? (max_iters > 1 ? 2 : 0) : 1) : -1);
+      if (rc != BANET_OK) return rc;
+      {
+        RangeScope r("solve", lv->N);
+        rc = launch_solve(a, s);
+      }
+      if (rc != BANET_OK) return rc;
+    }
   }
   return BANET_OK;
 }
@@ -231,8 +323,6 @@ void banet_lm_params_default(banet_lm_params_t* p) {
   p->solver = BANET_SOLVER_QR;                          // legacy/ba.py:9
 }
 
-constexpr int kRoleSmallLevel = 19200;   // pixels: levels whose SYRK launch is latency-bound (see the role condition below)
-
 int banet_lm_level_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters,
                        int early_termination, banet_state_t* st, void* ws, size_t ws_bytes, banet_stream_t stream) {
   return banet_lm_level_ex_f32(lv, mlp, l2_base, max_iters, early_termination, nullptr, st, ws, ws_bytes, stream);
@@ -241,81 +331,10 @@ int banet_lm_level_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2
 int banet_lm_level_ex_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters,
                           int early_termination, const banet_lm_params_t* params, banet_state_t* st, void* ws,
                           size_t ws_bytes, banet_stream_t stream) {
-  int rc = check_level(lv);
+  LevelRun run;
+  const int rc = lm_level_plan(lv, mlp, l2_base, max_iters, early_termination, params, st, ws, ws_bytes, &run);
   if (rc != BANET_OK) return rc;
-  rc = check_state(lv, mlp, st);
-  if (rc != BANET_OK) return rc;
-  if (max_iters < 0) return BANET_ERR_INVALID_ARG;
-  AsmPlan pl;
-  rc = plan_assemble(lv, num_cus(), &pl);
-  if (rc != BANET_OK) return rc;
-  if (!ws || !aligned256(ws)) return BANET_ERR_WORKSPACE;
-  LevelWs w = carve_level(lv, pl, ws);
-  if (ws_bytes < w.total) return BANET_ERR_WORKSPACE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  SolveArgs a = make_solve_args(lv, mlp, l2_base, w.AtA, w.Atb, w.absres, w.nvalid, st);
-  a.max_iters = max_iters;
-  a.bigA = w.bigA;
-  if (params) {
-    if (params->solver != BANET_SOLVER_QR && params->solver != BANET_SOLVER_INVERSE) return BANET_ERR_INVALID_ARG;
-    if (!(params->angle_change >= 0.f) || !(params->translation_change >= 0.f) || !(params->residual_ratio > 0.f))
-      return BANET_ERR_INVALID_ARG;   // also rejects NaN
-    a.lm = *params;
-  }
-  const bool lm = early_termination && lv->variant == BANET_LEGACY_LM;
-  if (lm) {
-    // device-side loop control: max_iters + 1 evaluation rounds; the last one only runs the
-    // pending accept/reject test (legacy/ba.py:304-345), see solve.hip
-    launch_ctl_init(w.ctl, st->iters, lv->B, s);
-    a.ctl = w.ctl;
-    const int stride = (int)(sizeof(LmCtl) / sizeof(int32_t));
-    for (int it = 0; it <= max_iters; ++it) {
-      rc = launch_assemble(lv, pl, st->R, st->T, st->Wc, &w.ctl->active, stride, w.partials, w.AtA, w.Atb, w.absres,
-                           w.nvalid, s);
-      if (rc != BANET_OK) return rc;
-      {
-        RangeScope r("solve", lv->N);
-        rc = launch_solve(a, s);
-      }
-      if (rc != BANET_OK) return rc;
-    }
-  } else {
-    launch_zero_iters(st->iters, lv->B, s);
-    // the tile queue is reset once here; afterwards every solve kernel leaves it zeroed for the next gather
-    a.queue = assemble_queue(pl, w.partials);
-    a.nqueue = 8 * npairs(lv);
-    if (a.queue) launch_zero_iters(a.queue, lv->B * a.nqueue, s);   // a kernel, not hipMemsetAsync: see prepare_gather
-    // bundle levels whose SYRK is ba_syrk_bf16x6_kernel: the lambda MLP runs as a role workgroup of the SYRK launch, off the
-    // solve kernel's critical path (C <= 256: the role's LDS scratch)
-    // ... and coarse levels at any batch (N <= kRoleSmallLevel pixels: their SYRK is a latency chain of 1-3 steps per wave, so a
-    // window's 7 workgroups take what 8 take, and the solve kernel loses the 19 us MLP: 40x30 .. 160x120 x 32 windows).
-    // Small batches only (B <= 8) otherwise: the SYRK kernel runs one workgroup per CU (512 registers per wave), so the role workgroups
-    // need CUs of their own -- at B = 32 (8 + 1 workgroups per window = 288 > 256 CUs) a second round of workgroups doubled
-    // the SYRK time (640x480 x 32: 1326 -> 2457 us); with B <= 8 one SYRK workgroup per window is given up where needed.
-    const int Bsel = selection_batch(lv);   // (the role changes Gs, i.e. the summation split: decided like every other selection)
-    const bool role = lv->variant == BANET_BUNDLE && mlp != nullptr && a.use_mlp && syrk_runs_mlp_role(pl.s) && lv->C <= 256 &&
-                      (lv->C & 3) == 0 && ((long long)Bsel * (pl.s.Gs + 1) <= num_cus() || (Bsel <= 8 && pl.s.Gs >= 16) ||
-                       (lv->N <= kRoleSmallLevel && pl.s.Gs >= 4)) &&
-                      !(lv->flags & kDevMlpInSolve);   // MLP inside the solve kernel (A/B)
-    if (role) {
-      a.mlp_y = w.mlp_y;
-      if ((long long)Bsel * (pl.s.Gs + 1) > num_cus()) pl.s.Gs -= 1;
-    }
-    for (int it = 0; it < max_iters; ++it) {
-      rc = launch_assemble(lv, pl, st->R, st->T, st->Wc, nullptr, 0, w.partials, w.AtA, w.Atb, w.absres, w.nvalid, s,
-                           a.queue == nullptr, role ? mlp : nullptr, role ? w.mlp_y : nullptr, nullptr,
-                           // fp16 two-piece SYRK: the level's first pass runs the exact form and leaves the basis column maxima
-                           // on the way (no extra pass over the basis); a one-iteration call computes them up front instead
-                           pl.s.f16 ? (it == 0 ? (max_iters > 1 ? 2 : 0) : 1) : -1);
-      if (rc != BANET_OK) return rc;
-      {
-        RangeScope r("solve", lv->N);
-        rc = launch_solve(a, s);
-      }
-      if (rc != BANET_OK) return rc;
-    }
-  }
-  return BANET_OK;
+  return lm_level_enqueue(run, static_cast<hipStream_t>(stream));
 }
 
 int banet_resample_f32(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,

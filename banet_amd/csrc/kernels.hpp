@@ -160,4 +160,39 @@ int launch_small_step_adjoint(int variant, int B, int N, int C, int K, int pairs
                               const float* gT, const float* gW, float* gAtA, float* gAtb, float* gabs, float* dR, float* dT,
                               const banet_mlp_t* gmlp, void* ws, hipStream_t s);
 
+// ---- api.hip: one LM level as "validate + plan" and "enqueue" (banet_lm_level_ex_f32 = both; schedule.hip plans every level
+// of a schedule before it enqueues the first) ----
+struct LevelWs {  // carve of the level workspace
+  float* partials;
+  float* AtA;
+  float* Atb;
+  float* absres;
+  float* nvalid;
+  LmCtl* ctl;
+  float* mlp_y;   // [B] lambda-MLP outputs of the SYRK launch's role workgroups
+  float* bigA;
+  size_t total;
+};
+struct LevelRun {   // what lm_level_plan decided; host memory only
+  const banet_level_t* lv;
+  const banet_mlp_t* mlp;
+  AsmPlan pl;
+  LevelWs w;
+  SolveArgs a;
+  int max_iters;
+  bool lm;     // device-side loop control (BANET_LEGACY_LM with early termination)
+  bool role;   // the lambda MLP runs as a role workgroup of the SYRK launch
+};
+// every check of banet_lm_level_ex_f32, in its order and with its return codes; launches nothing
+int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, int early_termination,
+                  const banet_lm_params_t* params, const banet_state_t* st, void* ws, size_t ws_bytes, LevelRun* run);
+int lm_level_enqueue(const LevelRun& run, hipStream_t s);
+
+// ---- schedule.hip --------------------------------------------------------------------------
+struct TraceRow {   // one level's row of banet_solve_trace_t (nullptr: not recorded) next to the state it is copied from
+  banet_state_t from, to;
+  int nR, nT, K, P;   // floats per window: R (9 pairs), T (3 pairs), Wc, delta
+};
+void launch_lm_trace(const TraceRow& row, int B, hipStream_t s);
+
 }  // namespace banet

@@ -107,13 +107,37 @@ class DenseBA:
         T = T.reshape(B, -1, 3, 1) if self.pairs > 1 else T
         return ops.LmState(R, T, Wc if K > 0 else None, P=6 * self.pairs + K, pairs=self.pairs)
 
-    def solve(self, iters_per_level, state=None, early_termination=False, params=None, snapshots=None, level_events=None):
+    # True: solve() is one banet_lm_solve_f32 call (the level loop, the counts and the snapshots on the C side); False: the
+    # level loop below, one banet_lm_level_ex_f32 call per level.  Same bits either way.
+    c_schedule = True
+
+    def solve(self, iters_per_level, state=None, early_termination=False, params=None, snapshots=None, level_events=None,
+              depth_outputs=None):
         """Enqueue the full schedule; returns the state (R,T,Wc updated in place) and the list
         of per-level iteration-count tensors.  params: ops.lm_params(...) (legacy/ba.py:5-9) or None for the
-        reference's defaults.  snapshots: a list that receives, per level, a dict of clones of (R, T, W, delta, lam)
+        reference's defaults.  snapshots: a list that receives, per level, a dict of (R, T, W, delta, lam)
         after that level (device tensors, no host sync).  level_events: a list that receives one (start, end) pair of
-        torch.cuda.Event per level, recorded on the current stream (per-level times without a host sync)."""
+        torch.cuda.Event per level, recorded on the current stream (per-level times without a host sync).  depth_outputs: a list
+        that receives, per level, the depth map depth_l + basis_l . Wc after that level, shaped like the level's depth
+        (bundlenet.py:397 output_depths; `bundle` only)."""
         st = state if state is not None else self.new_state()
+        if depth_outputs is not None and self.variant != "bundle":
+            raise ops.capi.BanetError("DenseBA.solve: depth_outputs need the `bundle` variant (a depth basis)")
+        n = min(len(self.problems), len(iters_per_level))
+        if self.c_schedule and level_events is None and not self.split_coarse and 1 <= n <= 16:
+            # one call: counts / snapshots are views of the trace rows (allocated per call), nothing is cloned per level
+            depth = None
+            if depth_outputs is not None:
+                depth = [torch.empty((p.B, p.N), dtype=torch.float32, device=p.device) for p in self.problems[:n]]
+            trace = ops.SolveTrace(n, st, fields=None if snapshots is not None else ("iters",), depth=depth)
+            ops.lm_solve(self.problems[:n], self.mlps[:n], self.l2_base, list(iters_per_level[:n]), early_termination, st,
+                         ws=self.ws, params=params, trace=trace)
+            if snapshots is not None:
+                snapshots.extend(dict(R=trace.R[l], T=trace.T[l], W=None if trace.Wc is None else trace.Wc[l],
+                                      delta=trace.delta[l], lam=trace.lambda_out[l]) for l in range(n))
+            if depth_outputs is not None:
+                depth_outputs.extend(d.reshape(lv.depth.shape) for d, lv in zip(depth, self.levels))
+            return st, [trace.iters[l] for l in range(n)]
         counts = []
         for prob, mlp, its in zip(self.problems, self.mlps, iters_per_level):
             if level_events is not None:
@@ -142,6 +166,8 @@ class DenseBA:
             if snapshots is not None:
                 snapshots.append(dict(R=st.R.clone(), T=st.T.clone(), W=None if st.Wc is None else st.Wc.clone(),
                                       delta=st.delta.clone(), lam=st.lambda_out.clone()))
+            if depth_outputs is not None:
+                depth_outputs.append(ops.depth_output(prob.keep[2], prob.keep[3], st.Wc).reshape(self.levels[li].depth.shape))
         return st, counts
 
     def solve_differentiable(self, iters_per_level, R=None, T=None, Wc=None):

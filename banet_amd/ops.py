@@ -353,6 +353,84 @@ def lm_level_workspace_bytes(level):
     return capi.lib().banet_lm_level_workspace_bytes(ctypes.byref(level.c))
 
 
+class SolveTrace:
+    """banet_solve_trace_t plus the tensors it points at: the state after every level of one banet_lm_solve_f32 call, row l =
+    level l.  fields: which of R / T / Wc / lambda_out / delta / ratio / iters to record (default all; Wc only when the state has
+    one); depth: a list of n_levels tensors [B,N_l] (or None entries) that receive depth_l + basis_l . Wc after level l
+    (bundlenet.py:397; `bundle` only).  Attributes of fields that are not recorded are None."""
+    FIELDS = ("R", "T", "Wc", "lambda_out", "delta", "ratio", "iters")
+
+    def __init__(self, n_levels, state, fields=None, depth=None):
+        self.n_levels = int(n_levels)
+        self.c = capi.SolveTrace()
+        for name in self.FIELDS:
+            src = getattr(state, name)
+            t = None
+            if src is not None and (fields is None or name in fields):
+                t = torch.empty((self.n_levels,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+                setattr(self.c, name, t.data_ptr())
+            setattr(self, name, t)
+        self.depth = None
+        if depth is not None:
+            if len(depth) != self.n_levels:
+                raise capi.BanetError("SolveTrace: %d depth outputs for %d levels" % (len(depth), self.n_levels))
+            self.depth = list(depth)
+            self._depth_ptrs = (capi._FP * self.n_levels)(*[None if t is None else capi.ptr(t).value for t in self.depth])
+            self.c.depth = ctypes.cast(self._depth_ptrs, ctypes.POINTER(capi._FP))
+
+
+def _schedule(levels, mlps, l2_base, iters, early_termination, params, trace):
+    """-> (banet_schedule_t without a workspace, the ctypes arrays it points at)"""
+    n = len(levels)
+    if n == 0 or len(mlps) != n or len(iters) != n:
+        raise capi.BanetError("lm_solve: %d levels, %d lambda MLPs, %d iteration counts" % (n, len(mlps), len(iters)))
+    if trace is not None and trace.n_levels != n:
+        raise capi.BanetError("lm_solve: the trace has %d rows for %d levels" % (trace.n_levels, n))
+    lv = (capi.Level * n)(*[p.c for p in levels])         # (copies: later changes of a level's flags need a new call)
+    mp = (ctypes.POINTER(capi.Mlp) * n)()
+    for i, m in enumerate(mlps):
+        if m is not None:
+            m.check(levels[i].C)
+            mp[i] = ctypes.pointer(m.c)
+    it = (ctypes.c_int32 * n)(*[int(v) for v in iters])
+    s = capi.Schedule()
+    s.levels, s.n_levels = ctypes.cast(lv, ctypes.POINTER(capi.Level)), n
+    s.mlps = ctypes.cast(mp, ctypes.POINTER(ctypes.POINTER(capi.Mlp)))
+    s.max_iters = ctypes.cast(it, ctypes.POINTER(ctypes.c_int32))
+    s.l2_base, s.early_termination = float(l2_base), int(bool(early_termination))
+    if params is not None:
+        s.params = ctypes.pointer(params)
+    if trace is not None:
+        s.trace = ctypes.pointer(trace.c)
+    return s, (lv, mp, it, params, trace)
+
+
+def lm_solve_workspace_bytes(levels):
+    """banet_lm_solve_workspace_bytes: the maximum of the levels' needs (0: a level is unsupported or the levels disagree)"""
+    n = len(levels)
+    s = capi.Schedule()
+    lv = (capi.Level * max(n, 1))(*[p.c for p in levels])
+    s.levels, s.n_levels = ctypes.cast(lv, ctypes.POINTER(capi.Level)), n
+    return capi.lib().banet_lm_solve_workspace_bytes(ctypes.byref(s))
+
+
+def lm_solve(levels, mlps, l2_base, iters, early_termination, state, ws=None, params=None, trace=None):
+    """banet_lm_solve_f32: every level of a coarse -> fine schedule in ONE call -- the sequence of lm_level calls, bit for bit,
+    with the state after each level recorded in `trace` (a SolveTrace, or None).  levels / mlps / iters: one LevelProblem,
+    MlpWeights (or None) and iteration count per level.  All levels are validated before anything is enqueued."""
+    L = capi.lib()
+    s, keep = _schedule(levels, mlps, l2_base, iters, early_termination, params, trace)
+    nb = L.banet_lm_solve_workspace_bytes(ctypes.byref(s))
+    if nb == 0:
+        raise capi.BanetError("lm_solve: unsupported level shape, or levels that disagree in B / K / pairs / variant / policy")
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, levels[0].device)
+    s.workspace, s.workspace_bytes = ws.data_ptr(), ws.numel()
+    capi.check(L.banet_lm_solve_f32(ctypes.byref(s), ctypes.byref(state.c), capi.stream()))
+    del keep
+    return ws
+
+
 def profile_begin(max_launches):
     capi.check(capi.lib().banet_profile_begin(int(max_launches)))
 

@@ -268,6 +268,56 @@ int banet_lm_level_ex_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float
                           int max_iters, int early_termination, const banet_lm_params_t* params,
                           banet_state_t* st, void* ws, size_t ws_bytes, banet_stream_t stream);
 
+/* (5c) the whole coarse -> fine schedule in one call.  The reference's layer runs every level inside one graph and returns the
+ *     per-level rotations, translations and depths of all of them (bundlenet.py:376-399: the loop over the pyramid and its
+ *     output_rotations / output_translations / output_depths lists; legacy/ba.py:106-145: trackTF's three levels and their
+ *     iteration counts).  banet_lm_solve_f32 is exactly the sequence
+ *         banet_lm_level_ex_f32(&levels[l], mlps[l], l2_base, max_iters[l], early_termination, params, st,
+ *                               workspace, workspace_bytes, stream)        for l = 0 .. n_levels - 1
+ *     on one stream, with the state after each level copied into row l of the trace -- bit-identical to that sequence plus
+ *     copies after every level.  The levels are PREPARED levels, dense or sparse (the per-level resampling of (6) is the
+ *     caller's); they share B, K, pairs, variant and policy (the state's layout) and may differ in H, W, N, C, scale, flags.
+ *       - all or nothing: every level, the state, params, each level's launch plan and workspace need are checked on the host
+ *         before the first launch; a bad level -- also the last one -- returns the code banet_lm_level_ex_f32 would return for
+ *         it and nothing has been enqueued.  Levels that disagree in B / K / pairs / variant / policy, n_levels outside 1 .. 16,
+ *         trace->depth with a variant other than BANET_BUNDLE: BANET_ERR_INVALID_ARG;
+ *       - workspace: the MAXIMUM of the levels' banet_lm_level_workspace_bytes (banet_lm_solve_workspace_bytes; 0 = a level is
+ *         invalid or unsupported, or the levels disagree).  Each level runs on the previous level's leftovers (the scratch
+ *         contract at the top of this file); the trace needs none;
+ *       - trace: every pointer optional (NULL = not recorded); one small kernel per level (no memcpy nodes), the per-level depth
+ *         through the kernel of banet_depth_output_f32;
+ *       - no allocation, no synchronisation, no global state, one stream: capturable into a HIP graph as a linear chain.
+ *     BANET_VERSION is unchanged by this addition: detect the entry by its symbol (dlsym / hasattr).                          */
+typedef struct banet_solve_trace { /* state AFTER each level; every pointer may be NULL */
+  float* R;            /* [n_levels][B][pairs][9]                                                */
+  float* T;            /* [n_levels][B][pairs][3]                                                */
+  float* Wc;           /* [n_levels][B][K]   (ignored when K == 0)                               */
+  float* lambda_out;   /* [n_levels][B]                                                          */
+  float* delta;        /* [n_levels][B][P]                                                       */
+  float* ratio;        /* [n_levels][B]                                                          */
+  int32_t* iters;      /* [n_levels][B]      the reference's iteration count at that level       */
+  float* const* depth; /* n_levels HOST-array entries, entry l NULL or a device buffer [B][N_l]:
+                          levels[l].depth + levels[l].basis . Wc after level l (bundlenet.py:397
+                          output_depths); BANET_BUNDLE only                                      */
+} banet_solve_trace_t;
+
+typedef struct banet_schedule {
+  const banet_level_t* levels;       /* n_levels prepared levels, coarse -> fine                 */
+  int32_t n_levels;                  /* 1 .. 16                                                  */
+  int32_t early_termination;         /* as banet_lm_level_f32's                                  */
+  const banet_mlp_t* const* mlps;    /* n_levels pointers (entries NULL where the variant has no
+                                        MLP: BANET_LEGACY_FIXED; the array itself may then be NULL) */
+  const int32_t* max_iters;          /* n_levels counts, each >= 0                               */
+  float l2_base;                     /* bundlenet.py:252-253 (1.0 for none)                      */
+  const banet_lm_params_t* params;   /* NULL = the reference's defaults                          */
+  void* workspace;                   /* >= banet_lm_solve_workspace_bytes, 256-byte aligned      */
+  size_t workspace_bytes;
+  const banet_solve_trace_t* trace;  /* NULL = nothing recorded                                  */
+} banet_schedule_t;
+
+size_t banet_lm_solve_workspace_bytes(const banet_schedule_t* s); /* reads levels / n_levels only */
+int banet_lm_solve_f32(const banet_schedule_t* s, banet_state_t* st, banet_stream_t stream);
+
 /* (6) per-level preparation -- the step immediately before the LM loop.
  *   banet_resample_f32   data [B,H,W,C], warp [B,N,2] (x,y) -> out [B,N,C]
  *       mode BANET_RESAMPLE_ZERO_PAD : tf.contrib.resampler.resampler as called at

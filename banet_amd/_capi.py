@@ -112,6 +112,12 @@ class Schedule(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_size_t), ("trace", ctypes.POINTER(SolveTrace))]
 
 
+class GridLevel(ctypes.Structure):
+    """mirror of banet_grid_level_t (banet_grid_resample[_grad]_f32: one level's pixel grid over the map)"""
+    _fields_ = [("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32), ("sx", ctypes.c_float), ("sy", ctypes.c_float),
+                ("ox", ctypes.c_float), ("oy", ctypes.c_float), ("out", _FP)]
+
+
 EXPORTS = {
     "banet_version": (ctypes.c_int, []),
     "banet_error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -124,6 +130,8 @@ EXPORTS = {
     "banet_depth_output_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 3 + [_FP]),
     "banet_resample_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
     "banet_resample_grad_f32": (ctypes.c_int, [_FP] * 5 + [ctypes.c_int] * 7 + [_FP, ctypes.c_size_t, _FP]),
+    "banet_grid_resample_f32": (ctypes.c_int, [_FP] + [ctypes.c_int] * 5 + [ctypes.POINTER(GridLevel), ctypes.c_int, _FP]),
+    "banet_grid_resample_grad_f32": (ctypes.c_int, [_FP] + [ctypes.c_int] * 5 + [ctypes.POINTER(GridLevel), ctypes.c_int, ctypes.c_int, _FP]),
     "banet_depth_output_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "banet_depth_output_grad_f32": (ctypes.c_int, [_FP] * 6 + [ctypes.c_int] * 4 + [_FP, ctypes.c_size_t, _FP]),
     "banet_sample_stats_blocks": (ctypes.c_int, [ctypes.c_int]),

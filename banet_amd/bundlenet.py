@@ -528,6 +528,82 @@ class BundleNet:
             out_D.append(self._depth_output(init_depth, basis, W))         # :397, differentiable w.r.t. init_depth / basis / W
         return out_R, out_T, out_D
 
+    # -- dense level drivers: every pixel of each chosen level is a point ----------------------
+    def _dense_levels(self, layers, levels, depth_map, basis_map, border):
+        """DenseLevel per chosen level: source layers[level], target the half-swapped batch, depth / basis from the decoder's maps
+        (which live at scale 2: half the finest level's resolution) through dense_prep.grid_pyramid"""
+        from . import dense, dense_prep
+        if border not in ("clamp", "zero"):
+            raise ValueError("border must be 'clamp' or 'zero', got %r" % (border,))
+        levels = [int(l) for l in levels]
+        scales = [2 ** (len(layers) - 1 - l) for l in levels]
+        shapes = [tuple(layers[l].shape[1:3]) for l in levels]
+        geoms = dense_prep.grid_levels(depth_map.shape[1], depth_map.shape[2], shapes, scales, 2)
+        clamp = border == "clamp"
+        depths = dense_prep.grid_pyramid(depth_map.detach(), geoms, clamp=clamp)          # stop_gradient, bundlenet.py:341
+        bases = dense_prep.grid_pyramid(basis_map, geoms, clamp=clamp) if basis_map is not None else [None] * len(levels)
+        dls = [dense.DenseLevel(s, layers[l], self._swap_halves(layers[l]), d, b)
+               for l, s, d, b in zip(levels, scales, depths, bases)]
+        return levels, dls
+
+    def _dense_solve(self, variant, intrisic, levels, dls, iters, R, T, extra=()):
+        """-> per level (R, T, W): one DenseBA.solve (the whole schedule in one C call) without gradients, DenseBA.solve_differentiable
+        when an input or a lambda weight requires grad"""
+        from . import dense
+        nbatch = dls[0].B
+        lws = [self.lambda_weights[str(l)] for l in levels]
+        intr = intrisic.reshape(nbatch, 4).detach()
+        ba = dense.DenseBA(intr, dls, [[(torch.as_tensor(w).detach(), torch.as_tensor(b).detach()) for w, b in lw] for lw in lws],
+                           variant=variant, l2_base=1000.0)
+        counts = [int(iters)] * len(dls)
+        tensors = [t for lv in dls for t in (lv.src, lv.tgt, lv.depth, lv.basis)] + [R, T] + list(extra)
+        for l in levels:
+            tensors += list(self._lambda_tensors(l))
+        if _wants_grad(*tensors):
+            ba.lambda_weights = lws                      # the tensors that may require grad
+            outs = []
+            ba.solve_differentiable(counts, R, T, None, outputs=outs)
+            return outs, True
+        snaps = []
+        ba.solve(counts, state=ba.new_state(R, T), snapshots=snaps)
+        return [(s["R"], s["T"], s["W"]) for s in snaps], False
+
+    def BundleResizeDense(self, intrisic, layers, basis, init_depth, init_rotation=None, init_translation=None, levels=(2, 3),
+                          iters=1, border="clamp", reuse_variables=False):
+        """bundlenet.py:332-399 with every pixel of each chosen level as a point (the dense solver, banet_amd/dense.py) instead of
+        sampled `points`: per level, the source map is layers[level], the target _swap_halves(layers[level]), and depth / basis are
+        the decoder's half-resolution `init_depth [B,Hh,Wh]` (detached, :341) and `basis [B,Hh,Wh,K]` resampled onto the level's
+        grid at `_points / 2` (:343-344) by one HIP launch for all levels.  `iters` BundleIterations per level with the instance's
+        lambda weights of that level, l2_regularizer_base 1000.  Returns (output_rotations, output_translations, output_depths),
+        one entry per level; output_depths[l] = init_depth + basis . W_l at the basis's resolution (:397).
+
+        intrisic [B,4,1] holds (fx, fy, ox, oy) of layers[-1]'s own pixel grid: the reference's hard-coded 320 x 256 crop
+        correction (:346-349) is NOT applied.  border="clamp" (default) clamps the taps of the resampled depth / basis into the map;
+        "zero" is tf.contrib.resampler's zero padding, under which the last row and column of an upsampled level (coordinates
+        beyond the map's last texel) keep half of their depth and basis.
+
+        Without gradients this is one DenseBA.solve; when layers, basis, init_depth, the initial pose or a lambda weight requires grad
+        it runs DenseBA.solve_differentiable, and gradients reach `basis` through the sampled levels AND the output depths,
+        `init_depth` through the output depths only."""
+        self.reuse_variables = reuse_variables
+        lvls, dls = self._dense_levels(layers, levels, init_depth, basis, border)
+        outs, graph = self._dense_solve("bundle", intrisic, lvls, dls, iters, init_rotation, init_translation, (init_depth, basis))
+        if graph:
+            from . import prep_grad
+            depth = [prep_grad.depth_output(init_depth, basis, W) for _, _, W in outs]
+        else:
+            nb, K = basis.shape[0], basis.shape[-1]
+            depth = [ops.depth_output(init_depth, basis.reshape(nb, -1, K), W) for _, _, W in outs]
+        return [o[0] for o in outs], [o[1] for o in outs], depth
+
+    def CameraResizeDense(self, intrisic, layers, _depths, levels=(0, 1, 2, 3), iters=1, border="clamp"):
+        """bundlenet.py:280-329 (pose only, `bundle_camera`) with every pixel of each chosen level as a point: depth levels from the
+        half-resolution `_depths [B,Hh,Wh]` (detached, :290) through dense_prep.grid_pyramid.  intrisic and border as
+        BundleResizeDense.  Returns (rotations, translations), one entry per level."""
+        lvls, dls = self._dense_levels(layers, levels, _depths, None, border)
+        outs, _ = self._dense_solve("bundle_camera", intrisic, lvls, dls, iters, None, None)
+        return [o[0] for o in outs], [o[1] for o in outs]
+
     # -- losses (bundlenet.py:401-463) ---------------------------------------------------
     def lossR(self, predQ, gtQ):
         return torch.mean(1.0 - (predQ * gtQ).sum(dim=1))            # tf.losses.cosine_distance

@@ -388,6 +388,18 @@ int banet_depth_output_grad_f32(const float* basis, const float* Wc, const float
                                   static_cast<hipStream_t>(stream));
 }
 
+int banet_grid_resample_f32(const float* data, int B, int H, int W, int C, int mode, const banet_grid_level_t* levels, int n_levels,
+                            banet_stream_t stream) {
+  return launch_grid_resample(data, B, H, W, C, mode, levels, n_levels, static_cast<hipStream_t>(stream));
+}
+
+int banet_grid_resample_grad_f32(float* ddata, int B, int H, int W, int C, int mode, const banet_grid_level_t* levels, int n_levels,
+                                 int flags, banet_stream_t stream) {
+  if (flags & ~BANET_ADJOINT_OVERWRITE) return BANET_ERR_INVALID_ARG;
+  return launch_grid_resample_grad(ddata, B, H, W, C, mode, levels, n_levels, flags & BANET_ADJOINT_OVERWRITE,
+                                   static_cast<hipStream_t>(stream));
+}
+
 int banet_sample_stats_blocks(int N) { return N > 0 ? sample_stats_blocks(N) : 0; }
 
 static bool sstats_shape_ok(int B, int N, int C, int H, int W) {

@@ -1,6 +1,7 @@
 // Launchers / argument blocks shared by the translation units of libbanet_hip.so (the host-only launch plans: plan.hpp).
 #pragma once
 #include "common.hpp"
+#include "grid_plan.hpp"   // the grid resampler's geometry (host-only like plan.hpp)
 
 namespace banet {
 
@@ -74,6 +75,13 @@ int launch_resample_grad(const float* data, const float* warp, const float* gout
 size_t depth_output_grad_workspace_bytes(int B, int N, int K);
 int launch_depth_output_grad(const float* basis, const float* Wc, const float* gout, float* dinit, float* dbasis, float* dWc, int B,
                              int N, int K, int overwrite, void* ws, hipStream_t s);
+
+// ---- grid_prep.hip: a map resampled onto the pixel grids of up to 8 levels, and the adjoint of all of them (no workspace) ----
+// both run every check of their C entry (banet_grid_resample[_grad]_f32) before the one launch
+int launch_grid_resample(const float* data, int B, int H, int W, int C, int mode, const banet_grid_level_t* levels, int n_levels,
+                         hipStream_t s);
+int launch_grid_resample_grad(float* ddata, int B, int H, int W, int C, int mode, const banet_grid_level_t* levels, int n_levels,
+                              int overwrite, hipStream_t s);
 
 // ---- eqcon.hip -------------------------------------------------------------------------
 void launch_reduce(const float* partials, int B, int G, int pstride, int P, float* AtA, float* Atb, hipStream_t s);

@@ -8,12 +8,11 @@
 // so every tap / row is a coalesced load.  Same operation order as the reference expressions
 // (the oracle restates them), fp32.
 #include "kernels.hpp"
+#include "resample_taps.hpp"
 
 namespace banet {
 
-// mode 0: tf.contrib.resampler -- zero padding, a point is sampled iff x > -1, y > -1, x < W, y < H;
-//         weights from the CEIL side (dx = cx - x), sum order a*f(fx,fy) + b*f(cx,cy) + c*f(fx,cy) + d*f(cx,fy)
-// mode 1: interpolate2d2 -- weights from the unclamped floor, indices clamped, ((a+b)+c)+d
+// the footprint (floor, weights, in-image tests) and the sum order of both modes: resample_taps.hpp, shared with grid_prep.hip
 __global__ __launch_bounds__(256) void ba_resample_kernel(const float* __restrict__ data, const float* __restrict__ warp,
                                                           float* __restrict__ out, int N, int C, int H, int W, int mode) {
   const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -22,40 +21,12 @@ __global__ __launch_bounds__(256) void ba_resample_kernel(const float* __restric
   for (int n = wv; n < N; n += nw) {   // one wave per point, lanes over channels
     const float x = warp[((size_t)b * N + n) * 2], y = warp[((size_t)b * N + n) * 2 + 1];
     float* o = out + ((size_t)b * N + n) * C;
-    if (mode == 0) {
-      const bool ok = (x > -1.f) && (y > -1.f) && (x < (float)W) && (y < (float)H);
-      const float xs = ok ? x : 0.f, ys = ok ? y : 0.f;
-      const float fxf = floorf(xs), fyf = floorf(ys), cxf = fxf + 1.f, cyf = fyf + 1.f;
-      const float dx = cxf - xs, dy = cyf - ys;
-      const int fx = (int)fxf, fy = (int)fyf, cx = (int)cxf, cy = (int)cyf;
-      auto in = [&](int xi, int yi) { return xi >= 0 && yi >= 0 && xi <= W - 1 && yi <= H - 1; };
-      auto at = [&](int xi, int yi) { return img + ((size_t)min(max(yi, 0), H - 1) * W + min(max(xi, 0), W - 1)) * C; };
-      const float* p00 = at(fx, fy);
-      const float* p11 = at(cx, cy);
-      const float* p01 = at(fx, cy);
-      const float* p10 = at(cx, fy);
-      const float m00 = in(fx, fy) ? 1.f : 0.f, m11 = in(cx, cy) ? 1.f : 0.f, m01 = in(fx, cy) ? 1.f : 0.f,
-                  m10 = in(cx, fy) ? 1.f : 0.f;
-      const float wa = dx * dy, wb = (1.f - dx) * (1.f - dy), wc = dx * (1.f - dy), wd = (1.f - dx) * dy;
-      for (int c = lane; c < C; c += 64) {
-        const float v = ((wa * (m00 * p00[c]) + wb * (m11 * p11[c])) + wc * (m01 * p01[c])) + wd * (m10 * p10[c]);
-        o[c] = ok ? v : 0.f;
-      }
-    } else {
-      const float x0f = floorf(x), y0f = floorf(y);
-      const float dx = x - x0f, dy = y - y0f;
-      const float w00 = (1.f - dx) * (1.f - dy), w01 = dx * (1.f - dy), w10 = (1.f - dx) * dy, w11 = dx * dy;
-      // NaN / inf coordinates: index 0 / saturated, like the oracle's nan_to_num before the clamp
-      const float xc = (x0f == x0f) ? fminf(fmaxf(x0f, -1e9f), 1e9f) : 0.f, yc = (y0f == y0f) ? fminf(fmaxf(y0f, -1e9f), 1e9f) : 0.f;
-      const int x0 = (int)xc, y0 = (int)yc;
-      const int xa = min(max(x0, 0), W - 1), xb = min(max(x0 + 1, 0), W - 1);
-      const int ya = min(max(y0, 0), H - 1), yb = min(max(y0 + 1, 0), H - 1);
-      const float* p00 = img + ((size_t)ya * W + xa) * C;
-      const float* p01 = img + ((size_t)ya * W + xb) * C;
-      const float* p10 = img + ((size_t)yb * W + xa) * C;
-      const float* p11 = img + ((size_t)yb * W + xb) * C;
-      for (int c = lane; c < C; c += 64) o[c] = ((p00[c] * w00 + p01[c] * w01) + p10[c] * w10) + p11[c] * w11;
-    }
+    const ResampleTaps t = resample_taps(x, y, H, W, mode);
+    const float* p0 = img + ((size_t)t.ty[0] * W + t.tx[0]) * C;
+    const float* p1 = img + ((size_t)t.ty[1] * W + t.tx[1]) * C;
+    const float* p2 = img + ((size_t)t.ty[2] * W + t.tx[2]) * C;
+    const float* p3 = img + ((size_t)t.ty[3] * W + t.tx[3]) * C;
+    for (int c = lane; c < C; c += 64) o[c] = resample_sum(t, mode, p0[c], p1[c], p2[c], p3[c]);
   }
 }
 

@@ -441,11 +441,13 @@ class _LevelSolve(torch.autograd.Function):
                 None if s_bas is None else dbasis.reshape(s_bas), gR.reshape(s_R), gT.reshape(s_T), gW) + tuple(glayers)
 
 
-def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=None, Wc=None):
+def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=None, Wc=None, outputs=None):
     """Differentiable DenseBA.solve with fixed iteration counts: `levels` = the DenseLevel objects `ba` was built from (their
     src / tgt / depth / basis tensors may require grad), `lambda_weights` = per level five (filters, biases) pairs (tensors
     that may require grad, or arrays).  Returns (R [B,3,3], T [B,3,1], Wc [B,K,1]) attached to the autograd graph
-    (multi-frame windows: R [B,pairs,3,3], T [B,pairs,3,1]; the pose-only `bundle_camera` variant: K = 0, Wc is empty)."""
+    (multi-frame windows: R [B,pairs,3,3], T [B,pairs,3,1]; the pose-only `bundle_camera` variant: K = 0, Wc is empty).
+    outputs: a list that receives (R, T, Wc) after each level, attached to the graph (the per-level outputs of
+    bundlenet.py:376-399; a level with no iterations repeats the state it was given)."""
     if ba.variant not in ("bundle", "bundle_camera"):
         raise capi.BanetError("solve_differentiable: bundle / bundle_camera variants only")
     dev = ba.intr.device
@@ -459,6 +461,8 @@ def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=
     Wc = torch.zeros(B, K, 1, device=dev) if Wc is None else Wc
     for li, (lv, lw, n_it) in enumerate(zip(levels, lambda_weights, iters_per_level)):
         if int(n_it) <= 0:
+            if outputs is not None:
+                outputs.append((R, T, Wc))
             continue
         flat = []
         for w, b in lw:
@@ -466,6 +470,8 @@ def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=
             flat += [w.reshape(w.shape[-2], w.shape[-1]), _to_param(b, dev).reshape(-1)]
         ba.mlps[li] = ops.MlpWeights([(flat[2 * i].detach(), flat[2 * i + 1].detach()) for i in range(5)], dev)
         R, T, Wc = _LevelSolve.apply(ba, li, int(n_it), lv.src, lv.tgt, lv.depth, lv.basis, R, T, Wc, *flat)
+        if outputs is not None:
+            outputs.append((R, T, Wc))
     return R, T, Wc
 
 

@@ -361,6 +361,32 @@ int banet_depth_output_grad_f32(const float* basis, const float* Wc, const float
                                 int B, int N, int K, int flags, void* ws, size_t ws_bytes,
                                 banet_stream_t stream);
 
+/* (6c) dense level preparation: a map resampled onto the PIXEL GRIDS of up to 8 pyramid levels, and the adjoint of all of them --
+ *     what bundlenet.py:343-344 and their gradients become when every pixel of a level is a BA point (the decoder's depth
+ *     and basis maps at every level's own resolution).  Level l's pixel (i, j) samples the map at
+ *         x = j sx + ox,  y = i sy + oy      (two float32 roundings each, never an fma: numpy float32 j * sx + ox)
+ *     with the mode, the footprint and the tap sum of banet_resample_f32; no warp tensor exists.
+ *   banet_grid_resample_f32       data [B,H,W,C] -> levels[l].out [B,Ho,Wo,C], every level in one launch.
+ *   banet_grid_resample_grad_f32  ddata [B,H,W,C] (= or +=) sum over the levels and over the output pixels whose taps include
+ *       the texel of tap weight x levels[l].out[b,i,j,:] (here the level's gout, read only); CLAMP: taps clamped onto one texel
+ *       each add their own weight.  One launch over the texels, each summed in a fixed order (levels ascending, then i, then j,
+ *       then the forward's tap order): no float atomics, bit-reproducible.  flags: BANET_ADJOINT_OVERWRITE writes every texel
+ *       (zeros where nothing lands); without it the sums are added to ddata.  Same bits as accumulating into zeros.
+ *   `levels` is a HOST array, copied into the kernel arguments.  Neither entry takes a workspace.  Supported geometry:
+ *   1 <= n_levels <= 8, 1 <= C <= 256, B <= 65535, 1/4 <= sx, sy <= 64, every sample coordinate of every level inside
+ *   [-1, W] x [-1, H], H W C and every Ho Wo C below 2^30 -- else BANET_ERR_UNSUPPORTED (BANET_ERR_INVALID_ARG for a NULL
+ *   pointer, a non-positive size or count, a non-finite or non-positive step, a non-finite offset, a bad mode or flag).
+ *   Every check happens before the launch.  16-byte accesses where C % 4 == 0 and every pointer is 16-byte aligned.          */
+typedef struct banet_grid_level {
+  int32_t Ho, Wo;      /* the level's grid */
+  float sx, sy, ox, oy;
+  float* out;          /* [B,Ho,Wo,C]; grad call: the level's gout, read only */
+} banet_grid_level_t;
+int banet_grid_resample_f32(const float* data, int B, int H, int W, int C, int mode,
+                            const banet_grid_level_t* levels, int n_levels, banet_stream_t stream);
+int banet_grid_resample_grad_f32(float* ddata, int B, int H, int W, int C, int mode,
+                                 const banet_grid_level_t* levels, int n_levels, int flags, banet_stream_t stream);
+
 /* (7) differentiable layer support -- the C-wide part of one BundleIteration / CameraIteration in the reference's
  *     own tensor layout (bundlenet.py:230-243) and its adjoint (what TF autodiff derives from the same statements),
  *     so that a training graph never materialises samp [B,N,3C], diff, grad or J [B,N,2,P]:

@@ -118,6 +118,11 @@ class GridLevel(ctypes.Structure):
                 ("ox", ctypes.c_float), ("oy", ctypes.c_float), ("out", _FP)]
 
 
+class ResidualOut(ctypes.Structure):
+    """mirror of banet_residual_out_t (banet_ba_residual_f32: per-pixel error maps, mask and their sums; proj / sums optional)"""
+    _fields_ = [("sq", _FP), ("ab", _FP), ("mask", _FP), ("proj", _FP), ("sums", _FP)]
+
+
 EXPORTS = {
     "banet_version": (ctypes.c_int, []),
     "banet_error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -140,6 +145,7 @@ EXPORTS = {
     "banet_ba_assemble_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),
     "banet_ba_assemble_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 7 + [_FP, ctypes.c_size_t, _FP]),
     "banet_ba_assemble_mask_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 8 + [_FP, ctypes.c_size_t, _FP]),
+    "banet_ba_residual_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(ResidualOut), _FP]),
     "banet_ba_solve_update_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float] + [_FP] * 4 +
                                   [ctypes.POINTER(State), _FP]),
     "banet_ba_solve_update_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),

@@ -273,6 +273,21 @@ int banet_ba_assemble_mask_f32(const banet_level_t* lv, const float* R, const fl
                          nullptr, nullptr, mask_out, pl.s.f16_standalone ? 0 : -1);
 }
 
+int banet_ba_residual_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_residual_out_t* out,
+                          banet_stream_t stream) {
+  // the checks of banet_ba_assemble_f32, in its order and with its codes (flags / policy only select kernels there: ignored here,
+  // but an unknown policy is refused like there)
+  int rc = check_level(lv);
+  if (rc != BANET_OK) return rc;
+  if (!R || !T || !out || !out->sq || !out->ab || !out->mask || (lv->K > 0 && !Wc)) return BANET_ERR_INVALID_ARG;
+  AsmPlan pl;
+  rc = plan_assemble(lv, num_cus(), &pl);
+  if (rc != BANET_OK) return rc;
+  rc = residual_shape_supported(lv);
+  if (rc != BANET_OK) return rc;
+  return launch_residual(lv, R, T, Wc, out, static_cast<hipStream_t>(stream));
+}
+
 int banet_ba_solve_update_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, const float* AtA,
                               const float* Atb, const float* absres, const float* nvalid, banet_state_t* st,
                               banet_stream_t stream) {

@@ -60,6 +60,11 @@ struct RangeScope {                         // pushes "banet.<role>[ N=<n>]" whe
 int profile_begin(int max_launches);
 int profile_end(int max_tags, int32_t* tag_points, int32_t* tag_launches, double* tag_ms, int32_t* ntags);
 
+// ---- residual.hip: per-pixel error maps, mask and their sums at a state (banet_ba_residual_f32; no workspace) ----
+int residual_shape_supported(const banet_level_t* lv);   // the assembly's launch-time refusals (odd C / K above 128), as its code
+int launch_residual(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_residual_out_t* out,
+                    hipStream_t s);
+
 // ---- prep.hip --------------------------------------------------------------------------
 int launch_resample(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,
                     hipStream_t s);

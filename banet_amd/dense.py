@@ -186,6 +186,33 @@ class DenseBA:
         ops.lm_level(self.problems[level_index], self.mlps[level_index], self.l2_base, 1, False, st, ws=self.ws)
         return st
 
+    def residual(self, level_index, state=None, R=None, T=None, Wc=None, proj=False):
+        """banet_ba_residual_f32 on level `level_index` at a state (an LmState, or R / T / Wc; default: new_state()) ->
+        ops.Residual(sq, ab [B,pairs,H,W] float32, mask [B,pairs,H,W] bool, proj [B,pairs,H,W,2] or None, sums [B,pairs,4] =
+        (sum sq, sum ab, in-image count, max sq) per window and target frame).  No host sync."""
+        st = state if state is not None else self.new_state(R, T, Wc)
+        p = self.problems[level_index]
+        r = ops.ba_residual(p, st.R, st.T, st.Wc if self.K > 0 else None, proj=proj, sums=True)
+        H, W = int(p.c.H), int(p.c.W)
+        shape = (p.B, p.pairs, H, W)
+        return ops.Residual(r.sq.reshape(shape), r.ab.reshape(shape), r.mask.reshape(shape).bool(),
+                            r.proj.reshape(shape + (2,)) if proj else None, r.sums)
+
+    def cost_trace(self, snapshots, state0=None):
+        """Did each level reduce the cost?  snapshots: what solve(snapshots=...) filled; state0: the state that solve started from
+        (default: new_state()).  -> [n_levels, 2, B, pairs, 4]: the sums (sum sq, sum ab, in-image count, max sq) of level l's
+        maps BEFORE that level (the state after level l - 1) and AFTER it.  Two launches per evaluation, no host sync."""
+        st0 = state0 if state0 is not None else self.new_state()
+        n = len(snapshots)
+        out = torch.empty((n, 2, self.B, self.pairs, 4), dtype=torch.float32, device=self.intr.device)
+        R, T, W = st0.R, st0.T, st0.Wc
+        for l, snap in enumerate(snapshots):
+            p = self.problems[l]
+            for k, (r_, t_, w_) in enumerate(((R, T, W), (snap["R"], snap["T"], snap["W"]))):
+                ops.ba_residual(p, r_, t_, w_ if self.K > 0 else None, sums=out[l, k])
+            R, T, W = snap["R"], snap["T"], snap["W"]
+        return out
+
     def algorithmic_bytes_per_iteration(self, level_index):
         """4*N_l*(C*F + K + 1) per window-iteration (F = 1 + pairs frames)."""
         p = self.problems[level_index]

@@ -2,6 +2,7 @@
 `util.equation_construction_grad`, bundlenet.py:76-82) and the fused entry points, each a
 thin call into libbanet_hip.so through its C ABI.  GPU only -- no CPU / eager fallback.
 """
+import collections
 import ctypes
 from typing import Tuple
 
@@ -308,6 +309,37 @@ def ba_assemble(level, R, T, Wc=None, return_mask=False):
                                        capi.ptr(Atb), capi.ptr(absres), capi.ptr(nvalid),
                                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), capi.stream()))
     return AtA, Atb, absres, nvalid
+
+
+Residual = collections.namedtuple("Residual", "sq ab mask proj sums")
+
+
+def ba_residual(problem, R, T, Wc=None, proj=False, sums=True):
+    """banet_ba_residual_f32: what the level costs at the state (R, T, Wc), per window, target frame and point ->
+    Residual(sq [B,pairs,N] = sum_c d^2, ab [B,pairs,N] = sum_c |d|, mask [B,pairs,N] uint8 (1 = in the image; sq = ab = 0 elsewhere),
+    proj [B,pairs,N,2] = (px, py) or None, sums [B,pairs,4] = (sum sq, sum ab, in-image count, max sq) or None).  sums may also be
+    a contiguous float32 device tensor of B * pairs * 4 elements to write into (it is returned).  Device tensors, no host sync, no
+    workspace; a window's bits do not depend on the batch."""
+    dev = problem.device
+    B, N, pairs = problem.B, problem.N, max(int(problem.c.pairs), 1)
+    R, T = capi.f32c(R), capi.f32c(T)
+    Wc = capi.f32c(Wc) if Wc is not None else None
+    pR, pT, pW = capi.ptr(R), capi.ptr(T), capi.ptr(Wc)      # (CPU tensors: BanetError, before anything is allocated)
+    if R.numel() != B * pairs * 9 or T.numel() != B * pairs * 3 or (Wc is not None and Wc.numel() != B * problem.K):
+        raise capi.BanetError("ba_residual: expected R [B,pairs,3,3], T [B,pairs,3,1], Wc [B,K,1] for B = %d, pairs = %d, K = %d"
+                              % (B, pairs, problem.K))
+    out = Residual(torch.empty((B, pairs, N), dtype=torch.float32, device=dev), torch.empty((B, pairs, N), dtype=torch.float32, device=dev),
+                   torch.empty((B, pairs, N), dtype=torch.uint8, device=dev),
+                   torch.empty((B, pairs, N, 2), dtype=torch.float32, device=dev) if proj else None,
+                   sums if torch.is_tensor(sums) else torch.empty((B, pairs, 4), dtype=torch.float32, device=dev) if sums else None)
+    if out.sums is not None and out.sums.numel() != B * pairs * 4:
+        raise capi.BanetError("ba_residual: sums must hold B * pairs * 4 = %d floats" % (B * pairs * 4))
+    c = capi.ResidualOut()
+    c.sq, c.ab, c.mask = out.sq.data_ptr(), out.ab.data_ptr(), out.mask.data_ptr()
+    c.proj = out.proj.data_ptr() if proj else None
+    c.sums = capi.ptr(out.sums).value if out.sums is not None else None
+    capi.check(capi.lib().banet_ba_residual_f32(ctypes.byref(problem.c), pR, pT, pW, ctypes.byref(c), capi.stream()))
+    return out
 
 
 def ba_solve_update(level, mlp, l2_base, AtA, Atb, absres, nvalid, state, ws=None):

@@ -217,6 +217,36 @@ int banet_ba_assemble_mask_f32(const banet_level_t* lv, const float* R, const fl
                                const float* Wc, float* AtA, float* Atb, float* absres, float* nvalid,
                                unsigned char* mask_out, void* ws, size_t ws_bytes, banet_stream_t stream);
 
+/* (3b) residual evaluation: what the level costs at the state (R, T, Wc), per pixel -- the reference's CheckUpdate
+ *     (legacy/ba.py:306-324: the masked average residual at a pose) as an op of its own, for every variant and per target frame.
+ *     For every window b, target frame f (pairs, as in banet_level_t) and point n:
+ *       D = depth[b,n] + basis[b,n,:] . Wc[b,:]  (K > 0), geometry and in-image mask by the float32 statements of the assembly
+ *       pass (3), F2w = the bilinear sample of the first C channels of target frame f (the +1 taps clamped to the image,
+ *       utils_python.py:96-99), d_c = F2w_c - F1_c with F1 the source row:
+ *         sq[b,f,n] = sum_c d_c^2     ab[b,f,n] = sum_c |d_c|     mask[b,f,n] = 1 in the image / 0
+ *         proj[b,f,n] = (px, py) as computed; unspecified where mask = 0           (optional)
+ *         sums[b,f,0..3] = sum_n sq, sum_n ab, sum_n mask (an integer count stored as float), max_n sq   (optional; a second
+ *                          launch over the three maps, one workgroup per (b, f), fixed order)
+ *     Every element of sq / ab / mask is written, zeros where mask = 0 (such a point, also one with a NaN projection, reads no
+ *     tap).  A window's bits -- sums included -- do not depend on the batch it is evaluated in: neither launch's arithmetic
+ *     depends on B, which is also why the entry takes NO workspace.  absres of (3) is sum over f and n of ab, per channel instead
+ *     of per pixel; nvalid of (3) is sum_f sums[b,f,2].
+ *     Accepts exactly the levels banet_ba_assemble_f32 accepts and refuses the others with its code (all four variants, dense
+ *     and sparse, pairs >= 1 for the bundle variants); a NULL lv / R / T / out / sq / ab / mask, or Wc with K > 0:
+ *     BANET_ERR_INVALID_ARG, decided before any launch.  lv->flags and lv->policy are accepted and ignored (a policy value (3)
+ *     refuses is refused here too).  Enqueue only: no
+ *     allocation, no synchronisation, no global state, one stream.  16-byte loads where C = 128 (K = 128) and src / tgt (basis)
+ *     are 16-byte aligned.  BANET_VERSION is unchanged by this addition: detect the entry by its symbol.                    */
+typedef struct banet_residual_out {
+  float* sq;            /* [B,pairs,N]   required */
+  float* ab;            /* [B,pairs,N]   required */
+  unsigned char* mask;  /* [B,pairs,N]   required */
+  float* proj;          /* [B,pairs,N,2] or NULL  */
+  float* sums;          /* [B,pairs,4]   or NULL  */
+} banet_residual_out_t;
+int banet_ba_residual_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc,
+                          const banet_residual_out_t* out, banet_stream_t stream);
+
 /* (4) lambda prediction + damping + solve + SE(3)/W update for all B windows
  *     (bundlenet.py:165-190,241-276; legacy/ba.py:187-213,266-302).  Consumes the outputs
  *     of (3); updates `st` in place.  l2_base: bundlenet.py:252-253 (pass 1.0 for none). */

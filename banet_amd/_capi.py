@@ -123,6 +123,18 @@ class ResidualOut(ctypes.Structure):
     _fields_ = [("sq", _FP), ("ab", _FP), ("mask", _FP), ("proj", _FP), ("sums", _FP)]
 
 
+class ResidualGradIn(ctypes.Structure):
+    """mirror of banet_residual_grad_in_t (banet_ba_residual_grad_f32: the upstream gradients of sq / ab / proj, each optional)"""
+    _fields_ = [("gsq", _FP), ("gab", _FP), ("gproj", _FP)]
+
+
+class ResidualGradOut(ctypes.Structure):
+    """mirror of banet_residual_grad_out_t (every output optional)"""
+    _fields_ = [("dsrc", _FP), ("dtgt", _FP), ("ddepth", _FP), ("dbasis", _FP), ("dWc", _FP), ("dR", _FP), ("dT", _FP)]
+
+
+ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2   # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
+
 EXPORTS = {
     "banet_version": (ctypes.c_int, []),
     "banet_error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -146,6 +158,9 @@ EXPORTS = {
     "banet_ba_assemble_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 7 + [_FP, ctypes.c_size_t, _FP]),
     "banet_ba_assemble_mask_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 8 + [_FP, ctypes.c_size_t, _FP]),
     "banet_ba_residual_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(ResidualOut), _FP]),
+    "banet_ba_residual_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.c_int]),
+    "banet_ba_residual_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(ResidualGradIn), ctypes.POINTER(ResidualGradOut),
+                                                  ctypes.c_int, _FP, ctypes.c_size_t, _FP]),
     "banet_ba_solve_update_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float] + [_FP] * 4 +
                                   [ctypes.POINTER(State), _FP]),
     "banet_ba_solve_update_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),

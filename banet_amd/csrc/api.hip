@@ -288,6 +288,39 @@ int banet_ba_residual_f32(const banet_level_t* lv, const float* R, const float* 
   return launch_residual(lv, R, T, Wc, out, static_cast<hipStream_t>(stream));
 }
 
+// the level checks of banet_ba_residual_f32, in its order and with its codes
+static int residual_level_check(const banet_level_t* lv) {
+  int rc = check_level(lv);
+  if (rc != BANET_OK) return rc;
+  AsmPlan pl;
+  rc = plan_assemble(lv, num_cus(), &pl);
+  if (rc != BANET_OK) return rc;
+  return residual_shape_supported(lv);
+}
+
+size_t banet_ba_residual_grad_workspace_bytes(const banet_level_t* lv, int want_dtgt) {
+  if (residual_level_check(lv) != BANET_OK) return 0;
+  if (want_dtgt && !residual_grad_dtgt_supported(lv)) return 0;
+  ResGradPlan pl;
+  plan_residual_grad(lv, want_dtgt != 0, &pl);
+  return pl.bytes;
+}
+
+int banet_ba_residual_grad_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_residual_grad_in_t* g,
+                               const banet_residual_grad_out_t* out, int flags, void* ws, size_t ws_bytes, banet_stream_t stream) {
+  int rc = check_level(lv);
+  if (rc != BANET_OK) return rc;
+  if (!R || !T || !g || !out || (!g->gsq && !g->gab && !g->gproj) || (lv->K > 0 && !Wc)) return BANET_ERR_INVALID_ARG;
+  if (flags & ~(BANET_ADJOINT_OVERWRITE | BANET_ADJOINT_OVERWRITE_MAP)) return BANET_ERR_INVALID_ARG;
+  rc = residual_level_check(lv);
+  if (rc != BANET_OK) return rc;
+  if (out->dtgt && !residual_grad_dtgt_supported(lv)) return BANET_ERR_UNSUPPORTED;
+  ResGradPlan pl;
+  plan_residual_grad(lv, out->dtgt != nullptr, &pl);
+  if (!ws || ws_bytes < pl.bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
+  return launch_residual_grad(lv, R, T, Wc, g, out, flags, ws, static_cast<hipStream_t>(stream));
+}
+
 int banet_ba_solve_update_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, const float* AtA,
                               const float* Atb, const float* absres, const float* nvalid, banet_state_t* st,
                               banet_stream_t stream) {

@@ -65,6 +65,18 @@ int residual_shape_supported(const banet_level_t* lv);   // the assembly's launc
 int launch_residual(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_residual_out_t* out,
                     hipStream_t s);
 
+// ---- residual_grad.hip: the backward of the above (banet_ba_residual_grad_f32) ----
+constexpr int kResGradLdsFrames = 32;   // windows of up to this many target frames keep the kernel's pose slots in LDS (16 x 12 doubles = 1536 bytes per frame)
+struct ResGradPlan {   // the workspace of one call; host memory only
+  int pairs, units, G, cols;   // G: workgroups = partial rows per window (512 points each); cols = 12 pairs + K floats per row
+  int slots_in_ws;             // pairs > kResGradLdsFrames: the pose slots [B][G][16][pairs][12] (doubles) live in the workspace
+  size_t off_part, off_slots, off_erow, off_eproj, off_rg, bytes;
+};
+bool residual_grad_dtgt_supported(const banet_level_t* lv);   // C-channel target map within the resampler gradient's limits
+void plan_residual_grad(const banet_level_t* lv, int want_dtgt, ResGradPlan* pl);   // a level the forward accepts
+int launch_residual_grad(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_residual_grad_in_t* gin,
+                         const banet_residual_grad_out_t* out, int flags, void* ws, hipStream_t s);
+
 // ---- prep.hip --------------------------------------------------------------------------
 int launch_resample(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,
                     hipStream_t s);

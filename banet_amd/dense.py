@@ -186,12 +186,24 @@ class DenseBA:
         ops.lm_level(self.problems[level_index], self.mlps[level_index], self.l2_base, 1, False, st, ws=self.ws)
         return st
 
-    def residual(self, level_index, state=None, R=None, T=None, Wc=None, proj=False):
+    def residual(self, level_index, state=None, R=None, T=None, Wc=None, proj=False, differentiable=False):
         """banet_ba_residual_f32 on level `level_index` at a state (an LmState, or R / T / Wc; default: new_state()) ->
         ops.Residual(sq, ab [B,pairs,H,W] float32, mask [B,pairs,H,W] bool, proj [B,pairs,H,W,2] or None, sums [B,pairs,4] =
-        (sum sq, sum ab, in-image count, max sq) per window and target frame).  No host sync."""
-        st = state if state is not None else self.new_state(R, T, Wc)
+        (sum sq, sum ab, in-image count, max sq) per window and target frame).  No host sync.
+        differentiable=True: the maps are attached to the autograd graph (ops.ba_residual_diff: gradients reach R / T / Wc as given
+        and the level's src / tgt / depth / basis tensors through banet_ba_residual_grad_f32); sums is then None."""
         p = self.problems[level_index]
+        if differentiable:
+            if state is not None:
+                R, T, Wc = state.R, state.T, state.Wc
+            elif R is None or T is None or (self.K > 0 and Wc is None):
+                st = self.new_state(R, T, Wc)
+                R, T, Wc = (st.R if R is None else R), (st.T if T is None else T), (st.Wc if Wc is None else Wc)
+            sq, ab, mask, pr = ops.ba_residual_diff(p, R, T, Wc if self.K > 0 else None, proj=proj)
+            shape = (p.B, p.pairs, int(p.c.H), int(p.c.W))
+            return ops.Residual(sq.reshape(shape), ab.reshape(shape), mask.reshape(shape).bool(),
+                                pr.reshape(shape + (2,)) if proj else None, None)
+        st = state if state is not None else self.new_state(R, T, Wc)
         r = ops.ba_residual(p, st.R, st.T, st.Wc if self.K > 0 else None, proj=proj, sums=True)
         H, W = int(p.c.H), int(p.c.W)
         shape = (p.B, p.pairs, H, W)

@@ -285,6 +285,25 @@ ADJOINT_REUSE_DEPTH_SEED = 8                          # banet_hip.h: BANET_ADJOI
 REUSE_MODE = os.environ.get("BANET_ADJOINT_REUSE", "1")   # "0": every frame's call recomputes z2 / zeta / e (A/B; same bits)
 
 
+def reprojection_loss(ba, level_index, R, T, Wc=None, kind="ab", reduce="mean"):
+    """A feature-metric reprojection loss on the per-pixel maps of level `level_index` of a DenseBA at the state (R, T, Wc) -> [B],
+    attached to the autograd graph (DenseBA.residual(differentiable=True): gradients reach R, T, Wc and the level's src / tgt /
+    depth / basis).  kind: "ab" = sum_c |d| or "sq" = sum_c d^2 per pixel and target frame.  reduce:
+      "mean" -- per window, the sum over frames and in-image pixels divided by their count;
+      "min"  -- per pixel the minimum over the frames that see it, then the mean over the pixels at least one frame sees.
+    A window no frame sees gives 0."""
+    if kind not in ("ab", "sq") or reduce not in ("mean", "min"):
+        raise capi.BanetError("reprojection_loss: kind is 'ab' or 'sq', reduce is 'mean' or 'min'")
+    r = ba.residual(level_index, R=R, T=T, Wc=Wc, differentiable=True)
+    m = r.mask.reshape(r.mask.shape[0], r.mask.shape[1], -1)
+    v = (r.ab if kind == "ab" else r.sq).reshape(m.shape)
+    if reduce == "mean":
+        return (v * m).sum((1, 2)) / m.sum((1, 2)).clamp(min=1)
+    seen = m.any(1)
+    best = torch.where(m, v, torch.full_like(v, float("inf"))).min(1).values
+    return torch.where(seen, best, torch.zeros_like(best)).sum(1) / seen.sum(1).clamp(min=1)
+
+
 def ADJOINT_TILE_SHAPE(k):
     """banet_hip.h: BANET_ADJOINT_TILE_SHAPE(k) -- development switch (A/B): 1 .. 5 = adj_tile_kernel with 8x4 / 4x4 / 8x2 / 8x7 / 4x2 texel tiles,
     8 .. 13 = adj_tile2_kernel (two visits per wave instruction) with 8x4 / 8x3 / 8x5 / 8x7 / 16x3 / 16x2; 0 = the default"""

@@ -342,6 +342,120 @@ def ba_residual(problem, R, T, Wc=None, proj=False, sums=True):
     return out
 
 
+RESIDUAL_GRAD_OUTPUTS = ("dsrc", "dtgt", "ddepth", "dbasis", "dWc", "dR", "dT")
+ResidualGrad = collections.namedtuple("ResidualGrad", RESIDUAL_GRAD_OUTPUTS)
+
+
+def _residual_grad_shapes(problem):
+    B, N, C, K, pairs = problem.B, problem.N, problem.C, problem.K, max(int(problem.c.pairs), 1)
+    H, W = int(problem.c.H), int(problem.c.W)
+    return dict(dsrc=(B, N, C), dtgt=(B, pairs, H, W, C), ddepth=(B, N), dbasis=(B, N, K), dWc=(B, K), dR=(B, pairs, 9), dT=(B, pairs, 3))
+
+
+def ba_residual_grad(problem, R, T, Wc, gsq=None, gab=None, gproj=None, want=RESIDUAL_GRAD_OUTPUTS, overwrite=True, into=None, ws=None):
+    """banet_ba_residual_grad_f32: the backward of ba_residual.  gsq, gab [B,pairs,N], gproj [B,pairs,N,2]: dL/dsq, dL/dab, dL/dproj
+    (None = zeros; at least one) -> ResidualGrad(dsrc [B,N,C], dtgt [B,pairs,H,W,C], ddepth [B,N], dbasis [B,N,K], dWc [B,K],
+    dR [B,pairs,9], dT [B,pairs,3]); the outputs not named in `want` (and dbasis / dWc of a level without a basis) are None.
+    overwrite=True: fresh tensors, every element written.  overwrite=False: dsrc / dtgt / ddepth / dbasis are ACCUMULATED into the
+    tensors given in `into` (a dict by output name; also with overwrite=True, to choose the destination); dR / dT / dWc are always
+    written.  dtgt needs a C-channel target map.  Device tensors, no host sync; bit-reproducible, a window's bits do not depend
+    on the batch."""
+    L = capi.lib()
+    dev = problem.device
+    B, N, K, pairs = problem.B, problem.N, problem.K, max(int(problem.c.pairs), 1)
+    R, T = capi.f32c(R), capi.f32c(T)
+    Wc = capi.f32c(Wc) if Wc is not None else None
+    pR, pT, pW = capi.ptr(R), capi.ptr(T), capi.ptr(Wc)
+    if R.numel() != B * pairs * 9 or T.numel() != B * pairs * 3 or (Wc is not None and Wc.numel() != B * K):
+        raise capi.BanetError("ba_residual_grad: expected R [B,pairs,3,3], T [B,pairs,3,1], Wc [B,K,1] for B = %d, pairs = %d, K = %d"
+                              % (B, pairs, K))
+    gin = capi.ResidualGradIn()
+    keep = []
+    for name, g, n in (("gsq", gsq, B * pairs * N), ("gab", gab, B * pairs * N), ("gproj", gproj, B * pairs * N * 2)):
+        if g is not None:
+            g = capi.f32c(g)
+            if g.numel() != n:
+                raise capi.BanetError("ba_residual_grad: %s must hold %d floats" % (name, n))
+            keep.append(g)
+            setattr(gin, name, capi.ptr(g).value)
+    unknown = [w for w in want if w not in RESIDUAL_GRAD_OUTPUTS]
+    if unknown:
+        raise capi.BanetError("ba_residual_grad: unknown outputs %s" % unknown)
+    shapes = _residual_grad_shapes(problem)
+    into = dict(into or {})
+    res, gout = {}, capi.ResidualGradOut()
+    for name in RESIDUAL_GRAD_OUTPUTS:
+        res[name] = None
+        if name not in want or (K == 0 and name in ("dbasis", "dWc")):
+            continue
+        t = into.get(name)
+        if t is None:
+            if not overwrite and name in ("dsrc", "dtgt", "ddepth", "dbasis"):
+                raise capi.BanetError("ba_residual_grad: overwrite=False accumulates into into[%r]" % name)
+            t = torch.empty(shapes[name], dtype=torch.float32, device=dev)
+        elif t.numel() != int(torch.Size(shapes[name]).numel()):
+            raise capi.BanetError("ba_residual_grad: into[%r] must hold %s" % (name, shapes[name]))
+        res[name] = t
+        setattr(gout, name, capi.ptr(t).value)
+    want_dtgt = res["dtgt"] is not None
+    nb = L.banet_ba_residual_grad_workspace_bytes(ctypes.byref(problem.c), int(want_dtgt))
+    if nb == 0 and want_dtgt and L.banet_ba_residual_grad_workspace_bytes(ctypes.byref(problem.c), 0) != 0:
+        raise capi.BanetError("ba_residual_grad: dtgt needs a C-channel target map (tgt_has_grad = 0) with C <= 256 and B pairs H W C < 2^32")
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, dev)
+    flags = (capi.ADJOINT_OVERWRITE | capi.ADJOINT_OVERWRITE_MAP) if overwrite else 0
+    capi.check(L.banet_ba_residual_grad_f32(ctypes.byref(problem.c), pR, pT, pW, ctypes.byref(gin), ctypes.byref(gout), flags,
+                                            ctypes.c_void_p(ws.data_ptr()), ws.numel(), capi.stream()))
+    return ResidualGrad(**res)
+
+
+class _ResidualDiff(torch.autograd.Function):
+    """ba_residual with banet_ba_residual_grad_f32 as its backward; the level tensors enter as inputs so that autograd sees them"""
+
+    @staticmethod
+    def forward(ctx, problem, want_proj, R, T, Wc, src, tgt, depth, basis):
+        r = ba_residual(problem, R, T, Wc, proj=True, sums=False)
+        ctx.problem = problem
+        ctx.shapes = [None if t is None else t.shape for t in (R, T, Wc, src, tgt, depth, basis)]
+        ctx.save_for_backward(R, T, *([Wc] if Wc is not None else []))
+        ctx.mark_non_differentiable(r.mask)
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None = a NULL upstream gradient
+        return r.sq, r.ab, r.mask, r.proj
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gsq, gab, _gmask, gproj):
+        problem = ctx.problem
+        saved = ctx.saved_tensors
+        R, T, Wc = saved[0], saved[1], (saved[2] if len(saved) > 2 else None)
+        need = ctx.needs_input_grad[2:]
+        names = ("dR", "dT", "dWc", "dsrc", "dtgt", "ddepth", "dbasis")
+        want = tuple(n for n, k in zip(names, need) if k)
+        if not want or (gsq is None and gab is None and gproj is None):
+            return (None,) * 9
+        g = ba_residual_grad(problem, R, T, Wc, gsq, gab, gproj, want=want, overwrite=True)
+        out = []
+        for n, k, shape in zip(names, need, ctx.shapes):
+            t = getattr(g, n) if k else None
+            out.append(None if t is None else t.reshape(shape))
+        return (None, None) + tuple(out)
+
+
+def ba_residual_diff(problem, R, T, Wc=None, proj=False):
+    """ba_residual attached to the autograd graph -> (sq, ab, mask, proj): sq, ab [B,pairs,N] and proj [B,pairs,N,2] (None unless
+    proj=True) are differentiable with respect to R, T, Wc and the tensors the problem was built from (src, tgt, depth, basis);
+    mask [B,pairs,N] uint8 is not.  The backward is one banet_ba_residual_grad_f32 call that asks only for the gradients some
+    input needs.  A level whose target map is the [f|gx|gy] layout has no target-map gradient: BanetError if that map requires
+    grad."""
+    src, tgt, depth, basis = problem.keep[0], problem.keep[1], problem.keep[2], problem.keep[3]
+    if tgt.requires_grad and int(problem.c.tgt_has_grad):
+        raise capi.BanetError("ba_residual_diff: no gradient for a [f|gx|gy] target map (tgt_has_grad = 1); detach it or pass the C-channel map")
+    R, T = capi.f32c(R), capi.f32c(T)
+    Wc = capi.f32c(Wc) if (Wc is not None and problem.K > 0) else None
+    sq, ab, mask, pr = _ResidualDiff.apply(problem, bool(proj), R, T, Wc, src, tgt, depth, basis)
+    return sq, ab, mask, (pr if proj else None)
+
+
 def ba_solve_update(level, mlp, l2_base, AtA, Atb, absres, nvalid, state, ws=None):
     """banet_ba_solve_update_f32: lambda, damping, solve, SE(3)/W update (in place on `state`).  Systems whose matrix does
     not fit the LDS (P > ~190) go through banet_ba_solve_update_ws_f32 with a workspace (`ws`, or one allocated here)."""

@@ -247,6 +247,52 @@ typedef struct banet_residual_out {
 int banet_ba_residual_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc,
                           const banet_residual_out_t* out, banet_stream_t stream);
 
+/* (3c) backward of (3b): the per-pixel maps as differentiable losses.  With upstream gradients gsq, gab [B,pairs,N] and
+ *     gproj [B,pairs,N,2] (each may be NULL = zeros; at least one is given) the loss is
+ *         L = sum_{b,f,n} gsq sq + gab ab + gproj . proj
+ *     with the forward's mask and the forward's floor of the projection held fixed (the one-sided derivative at an integer
+ *     coordinate, as banet_resample_grad_f32).  e_c = mask (2 gsq d_c + gab sgn d_c), sgn 0 = 0; a point with mask = 0 (also one
+ *     with a NaN projection) contributes nothing to any output and reads no tap, gproj is ignored there.
+ *       dsrc   [B,N,C]            = - sum_f e
+ *       dtgt   [B,pairs,H,W,C]    = per texel, the sum over the points' four taps of tap weight x e row (the +1 taps clamped as in
+ *                                   the forward; two clamped taps on one texel each add their own weight), in ascending
+ *                                   (point, tap) order -- the resampler gradient of (6b) in clamp mode with B pairs as its batch
+ *       ddepth [B,N] = dD_n       dbasis [B,N,K] = dD_n Wc_k       dWc [B,K] = sum_n dD_n basis[b,n,k]
+ *       dR [B,pairs,9], dT [B,pairs,3] = dL/dR (matrix entries, as dpose of (7b)), dL/dT
+ *     through (dpx, dpy) = sum_c e_c dF2w_c/d(px,py) + mask gproj and the forward's own float32 geometry statements.  No gradient
+ *     for rays or intrinsics.
+ *     Every output pointer may be NULL (not computed); a subset gives the same bits for that subset.  dR / dT / dWc are WRITTEN;
+ *     dsrc / ddepth / dbasis are accumulated (+=) unless flags has BANET_ADJOINT_OVERWRITE, dtgt unless BANET_ADJOINT_OVERWRITE_MAP
+ *     (overwriting writes every element, zeros where nothing lands: the same bits as accumulating into zeros); any other flag bit:
+ *     BANET_ERR_INVALID_ARG.  dbasis / dWc with K = 0 are ignored.
+ *     Accepts exactly the levels (3b) accepts, with its codes, decided before any launch; NULL lv / R / T / g / out, all three of
+ *     g's pointers NULL, or Wc NULL with K > 0: BANET_ERR_INVALID_ARG.  dtgt: C-channel target maps only (tgt_has_grad = 0) and
+ *     within the limits of (6b) with batch B pairs (C <= 256, B pairs H W C < 2^32), else BANET_ERR_UNSUPPORTED when out->dtgt is
+ *     given and workspace_bytes(lv, 1) = 0; the other outputs of such a level still work.
+ *     Workspace: required (the scratch contract at the top of this file), size by the query (want_dtgt = whether out->dtgt will be
+ *     given); NULL, misaligned or too small: BANET_ERR_WORKSPACE.  Enqueue only: no allocation, no synchronisation, no global
+ *     state, one stream, capturable.  No float atomics; bit-reproducible; every summation order depends on N, H, W and pairs, never
+ *     on B: a window's bits are the same alone and in any batch.  BANET_VERSION is unchanged: detect the entry by its symbol.
+ *     (BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP: the enum of (7b) below.)                                                      */
+typedef struct banet_residual_grad_in {
+  const float* gsq;   /* [B,pairs,N]   or NULL */
+  const float* gab;   /* [B,pairs,N]   or NULL */
+  const float* gproj; /* [B,pairs,N,2] or NULL */
+} banet_residual_grad_in_t;
+typedef struct banet_residual_grad_out { /* every pointer may be NULL */
+  float* dsrc;
+  float* dtgt;
+  float* ddepth;
+  float* dbasis;
+  float* dWc;
+  float* dR;
+  float* dT;
+} banet_residual_grad_out_t;
+size_t banet_ba_residual_grad_workspace_bytes(const banet_level_t* lv, int want_dtgt);
+int banet_ba_residual_grad_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc,
+                               const banet_residual_grad_in_t* g, const banet_residual_grad_out_t* out,
+                               int flags, void* ws, size_t workspace_bytes, banet_stream_t stream);
+
 /* (4) lambda prediction + damping + solve + SE(3)/W update for all B windows
  *     (bundlenet.py:165-190,241-276; legacy/ba.py:187-213,266-302).  Consumes the outputs
  *     of (3); updates `st` in place.  l2_base: bundlenet.py:252-253 (pass 1.0 for none). */

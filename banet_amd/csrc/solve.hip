@@ -216,7 +216,11 @@ __device__ void lu_solve_regs(float* A, int ld, int n, float* x, int* order, flo
         for (int u = 0; u < (kGrid * NR + 63) / 64; ++u) {
           const int i = tid + 64 * u;
           if (i < n) {
-            const float v = pv[i] ? -1.f : fabsf(cb[i]);
+            // a NaN candidate counts as the largest: `v > best` is false for a NaN, and a column whose unused rows are all NaN
+            // would leave no pivot at all (pi = 0x7fffffff, an index far outside pv[] / order[] / A) -- the poisoned row
+            // becomes the pivot instead and the result is NaN, as documented
+            const float av = fabsf(cb[i]);
+            const float v = pv[i] ? -1.f : (av == av ? av : __builtin_inff());
             if (v > best) {
               best = v;
               bi = i;
@@ -550,13 +554,14 @@ __device__ void rodrigues(const float w[3], bool clamp, float Rw[9], float V[9])
 // products (0.5 us each for the whole workgroup) where the blocked LDL^T is a 52 us chain of 9 panels x 3 barriers.  The
 // undamped last coefficient is eliminated exactly by a Schur step: A11 [x1 | z] = [b1 | a12] (both right-hand sides in the same
 // sweeps), x_last = (b_last - a12.x1) / (a_PP - a12.z), x = x1 - z x_last.  The matrix is only read; if the iteration
-// does not reach the tolerance within kPcgMaxIt products (small lambda: trained weights, other data) or meets a non-positive
-// curvature, the caller falls back to the LDL^T.  Fixed-order reductions: bit-reproducible.
+// does not reach the tolerance within kPcgMaxIt products (small lambda: trained weights, other data), meets a non-positive
+// curvature, or leaves a Schur complement below 2^-12 a_PP, the caller falls back to the LDL^T.  Fixed-order reductions: bit-reproducible.
 // Thread layout: 4 threads per row (16-byte row reads, quad reduction by DPP); x and r live in the row owner's registers,
 // only the search directions go through LDS.
 // --------------------------------------------------------------------------------------
 constexpr int kPcgMaxIt = 40;
 constexpr float kPcgTol2 = 2.5e-14f;     // (1.6e-7)^2 on |r|^2 / |b|^2
+constexpr float kPcgMinSchur = 1.f / 4096.f;   // smallest Schur complement of the undamped coefficient, relative to a_PP, that CG + Schur keeps
 
 // block-wide sums of NV values per thread (fixed order); sr: 16 * NV floats, a different buffer than the previous call's
 template <int NV>
@@ -655,16 +660,24 @@ __device__ bool pcg_schur_solve(const float* A, int ld, int n, bool undamped_las
     }
     __syncthreads();
   }
-  const bool ok = done0 && done1 && !bad;
+  bool ok = done0 && done1 && !bad;
   if (ok) {
     if (undamped_last) {
       float d[2] = {owner ? a12 * x0 : 0.f, owner ? a12 * x1 : 0.f};
       block_sum_n<2>(d, srB);
-      const float s = A[(size_t)(n - 1) * ld + n - 1] - d[1];
+      const float app = A[(size_t)(n - 1) * ld + n - 1];
+      const float s = app - d[1];
       const float t = A[(size_t)n * ld + n - 1] - d[0];
+      // The Schur complement is a difference of two numbers of the size of a_PP, and a12.z carries the error CG leaves in z: the
+      // recursively updated residual reaches the tolerance, the true one stagnates at the rounding of the products
+      // (~ sqrt(n1) 2^-24 per product, ~2^-20 of |z| after a handful).  Where more than half the significand cancels
+      // (s < 2^-12 a_PP: the last column all but a combination of the others) fewer than 8 bits of s are left, several times
+      // fewer than elimination keeps (P = 180, cond 5e6: 1.9e-1 against 4.0e-2): not CG's job either.  Uniform: s and a_PP are
+      // the same in every thread.  (s = a_PP = 0, the unobservable coefficient, stays here: 0 / 0 below.)
+      if (!(s >= kPcgMinSchur * app)) ok = false;
       const float xl = t / s;                                            // 0 / 0 when the coefficient is unobservable: NaN, as documented
-      if (owner) x[row] = x0 - x1 * xl;
-      if (tid == 0) x[n - 1] = xl;
+      if (ok && owner) x[row] = x0 - x1 * xl;
+      if (ok && tid == 0) x[n - 1] = xl;
     } else if (owner) {
       x[row] = x0;
     }

@@ -506,10 +506,10 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_bf16x6_kernel(const SyrkArg
   // of two from max word^2 / s.  Powers of two: the scaling and its inverse (epilogue) are exact.  Inputs that are not finite, or
   // exponents beyond what the inverse can undo, fall back to the exact bf16 form below (use16 = false, wave-uniform per window).
   [[maybe_unused]] float csc[4 * KH];       // this lane's columns 64 h + 4 m + e
-  [[maybe_unused]] float cmx[4 * KH];       // T0 = 1: running max |b| of those columns over this wave's pixels
+  [[maybe_unused]] unsigned cmx[4 * KH];    // T0 = 1: running max |b| of those columns over this wave's pixels, as float bits
   if constexpr (T0 == 1) {
 #pragma unroll
-    for (int c = 0; c < 4 * KH; ++c) cmx[c] = 0.f;
+    for (int c = 0; c < 4 * KH; ++c) cmx[c] = 0u;
   }
   [[maybe_unused]] float usc = 1.f, uinv = 1.f;
   [[maybe_unused]] bool use16 = false;
@@ -552,59 +552,146 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_bf16x6_kernel(const SyrkArg
   const int ns = (N + 31) >> 5, nwaves = a.Gs * kNumWaves, gw = g * kNumWaves + w;
   const int s0 = (int)(((long long)ns * gw) / nwaves), s1 = (int)(((long long)ns * (gw + 1)) / nwaves);
 
-  f32x4 pb[8][KH];
-  float ps[8][PAIRS], pu[8][NU];
-  auto issue = [&](int st) __attribute__((always_inline)) {
+  // raw registers of one 32-pixel step: basis rows, s and record words as loaded
+  struct Raw {
+    f32x4 pb[8][KH];
+    float ps[8][PAIRS], pu[8][NU];
+  };
+  Raw ra;
+  auto issue = [&](Raw& R, int st) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int pix = 32 * st + 8 * kq + i;
       const size_t p = (st < s1 && pix < N) ? (size_t)pix : 0;
 #pragma unroll
       for (int h = 0; h < KH; ++h)
-        pb[i][h] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bas_b + p * K + 64 * h + 4 * m));
+        R.pb[i][h] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bas_b + p * K + 64 * h + 4 * m));
 #pragma unroll
-      for (int pr = 0; pr < PAIRS; ++pr) ps[i][pr] = rec_b[((size_t)pr * N + p) * 8 + 6];
+      for (int pr = 0; pr < PAIRS; ++pr) R.ps[i][pr] = rec_b[((size_t)pr * N + p) * 8 + 6];
 #pragma unroll
-      for (int j = 0; j < NU; ++j) pu[i][j] = rec_b[p * 8 + uoff[j]];
+      for (int j = 0; j < NU; ++j) R.pu[i][j] = rec_b[p * 8 + uoff[j]];
     }
   };
 #ifdef BANET_TIMING
   unsigned long long tm0, tr0;
   asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(tm0), "=s"(tr0)::"memory");
 #endif
-  issue(s0);
   if constexpr (T0 == 16) {
     if (use16) {
-      for (int st = s0; st < s1; ++st) {
+      // ---- the fp16 loop.  One wave per SIMD issues its vector and matrix instructions one after the other, so a step costs what
+      // its instructions cost, and a good quarter of a step's vector instructions used to be sqrt(s) and usc / sqrt(s) of the lane's 8
+      // pixels -- the same 8 values in all 16 lanes of a pixel group.  Now lane l computes them for ONE pixel, 32 st + (l & 31),
+      // from one load of s per target frame, and the lanes fetch their 8 pixels' values across the wave: the same operations on
+      // the same operands, one instead of 8 square roots and divisions per lane and step.
+      // The loads are kept ahead of the split that consumes them, per instantiation:
+      //  * kTwoSets (K = 64): TWO sets of raw registers -- step st splits set st & 1 and issues step st + 2 into it before its MFMA
+      //    block, so a batch has a whole step plus an MFMA block to land.  (At K = 128 a second set does not fit: with one target
+      //    frame every formulation tried left 56-372 bytes of scratch per lane)
+      //  * kStagger (K = 128, one target frame): one set, refilled piecewise as the split frees it -- the records once the record
+      //    rows are split, the basis quads of column half h after half h -- so every piece has about half a split more to land and
+      //    some 8 KB per wave stay in flight throughout the split.  No extra registers.
+      //  * otherwise the refill follows the whole split, as in the exact loop.
+      // -DBANET_SYRK_SINGLE_BUFFER: the last form everywhere (A/B builds).
+#ifdef BANET_SYRK_SINGLE_BUFFER
+      constexpr bool kTwoSets = false, kStagger = false;
+#else
+      constexpr bool kTwoSets = KH == 1, kStagger = KH == 2 && PAIRS == 1;
+#endif
+      struct Raw16 {
+        f32x4 pb[8][KH];
+        float ps1[PAIRS], pu[8][NU];
+      };
+      Raw16 r0;
+      [[maybe_unused]] Raw16 r1;
+      const int l32 = lane & 31;
+      // A refill's step index is made to depend on the split results that free its registers (an empty asm: no instruction), and
+      // a scheduling barrier follows it: the compiler may then neither hoist the loads above the split (it did, and spilled the
+      // values they would overwrite) nor sink them towards the MFMA block.  The waits stay the compiler's counted vmcnt.
+      auto after = [](int st_, const u32x4& x) __attribute__((always_inline)) {
+        asm volatile("" : "+s"(st_) : "v"(x));
+        return st_;
+      };
+      // the pieces of a refill; pixels past the run or the window repeat row 0, as in issue()
+      auto row_of = [&](int st_, int o) __attribute__((always_inline)) {
+        const int lim = st_ < s1 ? N : 0;      // (one scalar select: as a condition of its own the compiler branches on it per load)
+        const unsigned pix = 32 * st_ + o;
+        return (size_t)((int)pix < lim ? pix : 0u);
+      };
+      auto issue_rec = [&](Raw16& R, int st_) __attribute__((always_inline)) {
+        const size_t p1 = row_of(st_, l32);
+#pragma unroll
+        for (int pr = 0; pr < PAIRS; ++pr) R.ps1[pr] = rec_b[((size_t)pr * N + p1) * 8 + 6];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const size_t p = row_of(st_, 8 * kq + i);
+#pragma unroll
+          for (int j = 0; j < NU; ++j) R.pu[i][j] = rec_b[p * 8 + uoff[j]];
+        }
+      };
+      auto issue_rows = [&](Raw16& R, int st_, int h) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          R.pb[i][h] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(bas_b + row_of(st_, 8 * kq + i) * K + 64 * h + 4 * m));
+      };
+      auto issue16 = [&](Raw16& R, int st_) __attribute__((always_inline)) {   // always in this order: the counted waits at the loop
+        issue_rec(R, st_);                                                      // head are merged over the prologue and the back edge
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int h = 0; h < KH; ++h) {
+          issue_rows(R, st_, h);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      // one step: split set R (step st), refill it, multiply
+      auto step16 = [&](Raw16& R, int st) __attribute__((always_inline)) {
         float sq[8];
         u32x4 opu[NU][2];
         {
+          float ssum = R.ps1[0];
+#pragma unroll
+          for (int pr = 1; pr < PAIRS; ++pr) ssum += R.ps1[pr];
+          const float sq1 = 32 * st + l32 < N ? sqrtf(fmaxf(ssum, 0.f)) : 0.f;          // zero switches the pixel off
+          const float inv1 = sq1 > 0.f ? usc / sq1 : 0.f;
           float ut[NU][8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
-            const bool ok = 32 * st + 8 * kq + i < N;
-            float ssum = ps[i][0];
+            sq[i] = __shfl(sq1, 8 * kq + i, 64);
+            const float inv = __shfl(inv1, 8 * kq + i, 64);
 #pragma unroll
-            for (int pr = 1; pr < PAIRS; ++pr) ssum += ps[i][pr];
-            sq[i] = ok ? sqrtf(fmaxf(ssum, 0.f)) : 0.f;          // zero switches the pixel off
-            const float inv = sq[i] > 0.f ? usc / sq[i] : 0.f;
-#pragma unroll
-            for (int j = 0; j < NU; ++j) ut[j][i] = uon[j] ? pu[i][j] * inv : 0.f;
+            for (int j = 0; j < NU; ++j) ut[j][i] = uon[j] ? R.pu[i][j] * inv : 0.f;
           }
 #pragma unroll
           for (int j = 0; j < NU; ++j) split8_f16x2(ut[j], opu[j]);
         }
+        [[maybe_unused]] int stn = st + (kTwoSets ? 2 : 1);
+        if constexpr (kTwoSets || kStagger) {
+#pragma unroll
+          for (int j = 0; j < NU; ++j) stn = after(stn, opu[j][1]);
+        }
+        if constexpr (kStagger) {
+          issue_rec(R, stn);                                    // s and the record words are free
+          __builtin_amdgcn_sched_barrier(0);
+        }
         u32x4 op[NBV][2];
 #pragma unroll
-        for (int h = 0; h < KH; ++h)
+        for (int h = 0; h < KH; ++h) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             float vv[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) vv[i] = (sq[i] * pb[i][h][e]) * csc[4 * h + e];
+            for (int i = 0; i < 8; ++i) vv[i] = (sq[i] * R.pb[i][h][e]) * csc[4 * h + e];
             split8_f16x2(vv, op[4 * h + e]);
           }
-        issue(st + 1);
+          if constexpr (kTwoSets || kStagger) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) stn = after(stn, op[4 * h + e][1]);
+          }
+          if constexpr (kStagger) {
+            issue_rows(R, stn, h);                              // the quads of column half h are free
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        if constexpr (!kStagger) issue16(R, stn);               // the set is free again (two sets: for the step after the next)
         __builtin_amdgcn_sched_barrier(0);
         // three products, smallest first, term-major (consecutive MFMAs write different accumulators): lo hi' + hi lo' + hi hi'
         constexpr int kFa[3] = {1, 0, 0}, kFb[3] = {0, 1, 0};
@@ -627,9 +714,24 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_bf16x6_kernel(const SyrkArg
             }
         }
         __builtin_amdgcn_sched_barrier(0);
+      };
+      issue16(r0, s0);
+      if constexpr (kTwoSets) {
+        issue16(r1, s0 + 1);
+        int st = s0;
+        for (; st + 1 < s1; st += 2) {   // unrolled by two: the set of a step is a compile-time choice, both stay in registers
+          step16(r0, st);
+          step16(r1, st + 1);
+        }
+        if (st < s1) step16(r0, st);
+      } else {
+        for (int st = s0; st < s1; ++st) step16(r0, st);
       }
     }
   }
+  // the exact loop: T0 = 0 / 1 / 3, and the window-wide fallback of T0 = 16 (from step s0, with loads of its own)
+  const bool exact_loop = !(T0 == 16 && use16);
+  if (exact_loop) issue(ra, s0);
   for (int st = (T0 == 16 && use16) ? s1 : s0; st < s1; ++st) {
     // ---- H_cd / Atb_d on the bf16 pipe too: sum u b = sum (u / sqrt(s)) (sqrt(s) b) = sum u~ v with the SAME split v
     // as H_dd (|u| <= sqrt(Jc^T M Jc) sqrt(s): u~ is bounded, and s = 0 implies M jd = 0, i.e. u = r = 0 exactly).
@@ -641,13 +743,13 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_bf16x6_kernel(const SyrkArg
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const bool ok = 32 * st + 8 * kq + i < N;
-        float ssum = ps[i][0];
+        float ssum = ra.ps[i][0];
 #pragma unroll
-        for (int pr = 1; pr < PAIRS; ++pr) ssum += ps[i][pr];
+        for (int pr = 1; pr < PAIRS; ++pr) ssum += ra.ps[i][pr];
         sq[i] = ok ? sqrtf(fmaxf(ssum, 0.f)) : 0.f;          // zero switches the pixel off
         const float inv = sq[i] > 0.f ? 1.f / sq[i] : 0.f;
 #pragma unroll
-        for (int j = 0; j < NU; ++j) ut[j][i] = uon[j] ? pu[i][j] * inv : 0.f;
+        for (int j = 0; j < NU; ++j) ut[j][i] = uon[j] ? ra.pu[i][j] * inv : 0.f;
       }
 #pragma unroll
       for (int j = 0; j < NU; ++j) split8_bf16x3(ut[j], opu[j]);
@@ -660,17 +762,18 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_bf16x6_kernel(const SyrkArg
       for (int e = 0; e < 4; ++e) {
         float vv[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) vv[i] = sq[i] * pb[i][h][e];
+        for (int i = 0; i < 8; ++i) vv[i] = sq[i] * ra.pb[i][h][e];
         split8_bf16x3(vv, op[4 * h + e]);
         if constexpr (T0 == 1) {
 #pragma unroll
-          for (int i = 0; i < 8; ++i) {   // (rows past N repeat row 0)  NaN-sticky like ba_colmax_kernel (fmaxf would drop a NaN and the
-            const float av = fabsf(pb[i][h][e]);   // not-finite fallback of the fp16 form would then depend on who computed the maxima)
-            cmx[4 * h + e] = (av > cmx[4 * h + e] || av != av) ? av : cmx[4 * h + e];
+          for (int i = 0; i < 8; i += 2) {   // (rows past N repeat row 0)  On the bit patterns of |b|: they order like unsigned integers
+            const unsigned a0 = __float_as_uint(ra.pb[i][h][e]) & 0x7fffffffu;       // and a NaN lies above every finite value, so it
+            const unsigned a1 = __float_as_uint(ra.pb[i + 1][h][e]) & 0x7fffffffu;   // sticks as in ba_colmax_kernel (fmaxf would drop it).
+            cmx[4 * h + e] = max(cmx[4 * h + e], max(a0, a1));                       // One three-input unsigned max per two values.
           }
         }
       }
-    issue(st + 1);                                          // the raw registers are free again
+    issue(ra, st + 1);                                      // the raw registers are free again
     __builtin_amdgcn_sched_barrier(0);                      // keep the prefetch ahead of the MFMA block
     // Term-major order: consecutive MFMAs write DIFFERENT accumulators.  Block-major (six dependent MFMAs in a row on
     // one accumulator) measured 19 cycles per MFMA instead of 16 and kept the wave stalled at issue behind each one.
@@ -710,7 +813,7 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_bf16x6_kernel(const SyrkArg
     unsigned* cm = reinterpret_cast<unsigned*>(const_cast<float*>(a.colmax)) + (size_t)b * K;     // (non-negative floats order like
 #pragma unroll                                                                                   //  unsigned integers; zeroed before)
     for (int c = 0; c < 4 * KH; ++c) {
-      unsigned v = __float_as_uint(cmx[c]);      // as bit patterns: |x| orders like an unsigned integer and a NaN stays the maximum
+      unsigned v = cmx[c];                       // bit patterns: |x| orders like an unsigned integer and a NaN stays the maximum
       v = max(v, (unsigned)__shfl_xor((int)v, 16, 64));
       v = max(v, (unsigned)__shfl_xor((int)v, 32, 64));
       if (kq == 0 && s1 > s0) atomicMax(&cm[64 * (c >> 2) + 4 * m + (c & 3)], v);

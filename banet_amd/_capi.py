@@ -133,6 +133,11 @@ class ResidualGradOut(ctypes.Structure):
     _fields_ = [("dsrc", _FP), ("dtgt", _FP), ("ddepth", _FP), ("dbasis", _FP), ("dWc", _FP), ("dR", _FP), ("dT", _FP)]
 
 
+class MarginalsOut(ctypes.Structure):
+    """mirror of banet_marginals_out_t (banet_ba_marginals_f32: pose_cov and status required, the others optional)"""
+    _fields_ = [("pose_cov", _FP), ("depth_var", _FP), ("wfactor", _FP), ("logdet", _FP), ("status", _FP)]
+
+
 ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2   # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
 
 EXPORTS = {
@@ -161,6 +166,8 @@ EXPORTS = {
     "banet_ba_residual_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.c_int]),
     "banet_ba_residual_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(ResidualGradIn), ctypes.POINTER(ResidualGradOut),
                                                   ctypes.c_int, _FP, ctypes.c_size_t, _FP]),
+    "banet_ba_marginals_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.c_int]),
+    "banet_ba_marginals_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(MarginalsOut), _FP, ctypes.c_size_t, _FP]),
     "banet_ba_solve_update_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float] + [_FP] * 4 +
                                   [ctypes.POINTER(State), _FP]),
     "banet_ba_solve_update_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),

@@ -321,6 +321,25 @@ int banet_ba_residual_grad_f32(const banet_level_t* lv, const float* R, const fl
   return launch_residual_grad(lv, R, T, Wc, g, out, flags, ws, static_cast<hipStream_t>(stream));
 }
 
+size_t banet_ba_marginals_workspace_bytes(const banet_level_t* lv, int want_depth_var) {
+  MargPlan pl;
+  if (plan_marginals(lv, want_depth_var, &pl) != BANET_OK) return 0;
+  return pl.bytes;
+}
+
+int banet_ba_marginals_f32(const banet_level_t* lv, const float* AtA, const float* damping, const float* sigma2,
+                           const banet_marginals_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream) {
+  if (!lv || !AtA || !out || !out->pose_cov || !out->status) return BANET_ERR_INVALID_ARG;
+  if (lv->B < 1 || lv->K < 0 || lv->pairs < 0) return BANET_ERR_INVALID_ARG;
+  const bool want_dv = out->depth_var != nullptr && lv->K > 0;   // depth_var / wfactor of a level without a basis: ignored
+  if (want_dv && (!lv->basis || lv->N < 1)) return BANET_ERR_INVALID_ARG;
+  MargPlan pl;
+  const int rc = plan_marginals(lv, want_dv, &pl);
+  if (rc != BANET_OK) return rc;
+  if (!ws || workspace_bytes < pl.bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
+  return launch_marginals(lv, pl, AtA, damping, sigma2, out, ws, static_cast<hipStream_t>(stream));
+}
+
 int banet_ba_solve_update_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, const float* AtA,
                               const float* Atb, const float* absres, const float* nvalid, banet_state_t* st,
                               banet_stream_t stream) {

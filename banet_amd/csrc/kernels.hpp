@@ -77,6 +77,19 @@ void plan_residual_grad(const banet_level_t* lv, int want_dtgt, ResGradPlan* pl)
 int launch_residual_grad(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_residual_grad_in_t* gin,
                          const banet_residual_grad_out_t* out, int flags, void* ws, hipStream_t s);
 
+// ---- marginals.hip: pose covariance and per-pixel depth variance from a normal matrix (banet_ba_marginals_f32) ----
+constexpr int kMargKMax = 256, kMargPMax = 304;   // the project's largest system (8 target frames, K = 256)
+struct MargPlan {   // the workspace of one call; host memory only
+  int P, m, K;      // m = 6 pairs pose coefficients
+  bool big;         // the factor kernel's matrix (packed lower triangle, doubles) lives in the workspace (P >= 200: it does not fit the LDS)
+  size_t lds;       // the factor kernel's dynamic LDS
+  size_t off_T, off_big, bytes;   // T = L_WW^-1 [B][K][K] for the depth-variance kernel
+};
+// reads lv->B / K / pairs only; BANET_ERR_INVALID_ARG (NULL, B < 1, negative K / pairs) or BANET_ERR_UNSUPPORTED (K > 256, P > 304)
+int plan_marginals(const banet_level_t* lv, int want_depth_var, MargPlan* pl);
+int launch_marginals(const banet_level_t* lv, const MargPlan& pl, const float* AtA, const float* damping, const float* sigma2,
+                     const banet_marginals_out_t* out, void* ws, hipStream_t s);
+
 // ---- prep.hip --------------------------------------------------------------------------
 int launch_resample(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,
                     hipStream_t s);

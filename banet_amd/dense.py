@@ -7,11 +7,14 @@ the whole coarse->fine LM schedule is enqueued on the current stream without a h
 Iteration bodies: `bundle` = bundlenet.py:193-278 (pose + depth basis), `bundle_camera` =
 bundlenet.py:122-191, `legacy_lm` / `legacy_fixed` = legacy/ba.py:226-345 / :148-214.
 """
+import collections
 import os
 
 import torch
 
 from . import ops
+
+DenseMarginals = collections.namedtuple("DenseMarginals", "pose_cov depth_var wfactor logdet status sigma2 damping")
 
 
 class DenseLevel:
@@ -209,6 +212,35 @@ class DenseBA:
         shape = (p.B, p.pairs, H, W)
         return ops.Residual(r.sq.reshape(shape), r.ab.reshape(shape), r.mask.reshape(shape).bool(),
                             r.proj.reshape(shape + (2,)) if proj else None, r.sums)
+
+    def marginals(self, level_index, state=None, R=None, T=None, Wc=None, damping=0.0, sigma2="residual",
+                  want=("pose_cov", "depth_var")):
+        """How sure is the solve?  The posterior marginals of level `level_index` at a state (an LmState, or R / T / Wc; default:
+        new_state()): one assembly pass (ops.ba_assemble, the exact SYRK form) for the normal matrix, then ops.ba_marginals ->
+        DenseMarginals(pose_cov [B,6 pairs,6 pairs], depth_var [B,H,W], wfactor, logdet, status [B], sigma2 [B] or None, damping [B]
+        or None -- the last two as they were passed on).
+        sigma2: "residual" = the residual variance at the state, sum_f sum sq / max(C sum_f count - P, 1) from residual().sums;
+        None = 1; a float or a tensor [B] is passed through.  damping: a float, a tensor [B], or "lambda" = state.lambda_out (the
+        last lambda of the solve).  No host sync."""
+        p = self.problems[level_index]
+        if isinstance(damping, str):
+            if damping != "lambda":
+                raise ops.capi.BanetError("DenseBA.marginals: damping is a number, a tensor or \"lambda\"")
+            if state is None:
+                raise ops.capi.BanetError("DenseBA.marginals: damping=\"lambda\" needs the solved state")
+            damping = state.lambda_out
+        st = state if state is not None else self.new_state(R, T, Wc)
+        wc = st.Wc if self.K > 0 else None
+        if isinstance(sigma2, str):
+            if sigma2 != "residual":
+                raise ops.capi.BanetError("DenseBA.marginals: sigma2 is None, a number, a tensor or \"residual\"")
+            sums = ops.ba_residual(p, st.R, st.T, wc, sums=True).sums
+            sigma2 = sums[:, :, 0].sum(dim=1) / torch.clamp(p.C * sums[:, :, 2].sum(dim=1) - float(p.P), min=1.0)
+        AtA = ops.ba_assemble(p, st.R, st.T, wc)[0]
+        m = ops.ba_marginals(p, AtA, damping=damping, sigma2=sigma2, want=want)
+        dv = m.depth_var.reshape(p.B, int(p.c.H), int(p.c.W)) if m.depth_var is not None else None
+        as_t = lambda v: v if (v is None or torch.is_tensor(v)) else torch.full((p.B,), float(v), dtype=torch.float32, device=p.device)
+        return DenseMarginals(m.pose_cov, dv, m.wfactor, m.logdet, m.status, as_t(sigma2), as_t(damping))
 
     def cost_trace(self, snapshots, state0=None):
         """Did each level reduce the cost?  snapshots: what solve(snapshots=...) filled; state0: the state that solve started from

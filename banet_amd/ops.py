@@ -342,8 +342,71 @@ def ba_residual(problem, R, T, Wc=None, proj=False, sums=True):
     return out
 
 
+MARGINALS_OUTPUTS = ("pose_cov", "depth_var", "wfactor", "logdet")
+Marginals = collections.namedtuple("Marginals", "pose_cov depth_var wfactor logdet status")
+
+
+def ba_marginals_workspace_bytes(problem, want_depth_var=True):
+    """banet_ba_marginals_workspace_bytes (0 = unsupported: K > 256 or P > 304)"""
+    return int(capi.lib().banet_ba_marginals_workspace_bytes(ctypes.byref(problem.c), int(bool(want_depth_var))))
+
+
+def ba_marginals(problem, AtA, damping=None, sigma2=None, want=("pose_cov", "depth_var"), ws=None):
+    """banet_ba_marginals_f32: how well the normal equations AtA [B,P,P] (ba_assemble) determine their answer.  With
+    H = AtA + damping diag(diag(AtA) + 1e-5) (every diagonal entry) and Sigma = sigma2 H^-1 ->
+    Marginals(pose_cov [B,6 pairs,6 pairs] = the poses' joint marginal, depth_var [B,N] = the variance of depth + basis . Wc per
+    point, wfactor [B,K,K] = T lower triangular with Sigma_WW = sigma2 T^T T, logdet [B] = log det H, status [B] int32: 0, or 1
+    where H is not positive definite (that window: depth_var = +inf, pose_cov = +inf on the diagonal, wfactor = 0, logdet = -inf)).
+    damping, sigma2: None (0 and 1), a float, or a tensor [B].  `want` names the optional outputs to compute (pose_cov and status
+    always are; depth_var / wfactor of a level without a basis are None); the others are None.  `problem` needs .c (a
+    banet_level_t with B, N, K, pairs and basis set) only.  Device tensors, no host sync; a window's bits do not depend on the
+    batch nor on `want`."""
+    L = capi.lib()
+    lv = problem.c
+    B, N, K, pairs = int(lv.B), int(lv.N), int(lv.K), max(int(lv.pairs), 1)
+    m, P = 6 * pairs, 6 * pairs + K
+    AtA = capi.f32c(AtA)
+    pA = capi.ptr(AtA)                      # (a CPU tensor: BanetError, before anything is allocated)
+    dev = AtA.device
+    if AtA.numel() != B * P * P:
+        raise capi.BanetError("ba_marginals: AtA must be [B,P,P] = [%d,%d,%d]" % (B, P, P))
+    unknown = [w for w in want if w not in MARGINALS_OUTPUTS]
+    if unknown:
+        raise capi.BanetError("ba_marginals: unknown outputs %s" % unknown)
+
+    def per_window(v, name):
+        if v is None:
+            return None
+        t = v if torch.is_tensor(v) else torch.full((B,), float(v), dtype=torch.float32, device=dev)
+        t = capi.f32c(t).reshape(-1)
+        if t.numel() == 1 and B > 1:
+            t = t.expand(B).contiguous()
+        if t.numel() != B:
+            raise capi.BanetError("ba_marginals: %s must be a float or hold B = %d values" % (name, B))
+        return t
+
+    damping, sigma2 = per_window(damping, "damping"), per_window(sigma2, "sigma2")
+    pD, pS = capi.ptr(damping), capi.ptr(sigma2)
+    res = dict(pose_cov=torch.empty((B, m, m), dtype=torch.float32, device=dev),
+               depth_var=torch.empty((B, N), dtype=torch.float32, device=dev) if "depth_var" in want and K > 0 else None,
+               wfactor=torch.empty((B, K, K), dtype=torch.float32, device=dev) if "wfactor" in want and K > 0 else None,
+               logdet=torch.empty((B,), dtype=torch.float32, device=dev) if "logdet" in want else None,
+               status=torch.empty((B,), dtype=torch.int32, device=dev))
+    c = capi.MarginalsOut()
+    for name, t in res.items():
+        setattr(c, name, None if t is None else t.data_ptr())
+    nb = ba_marginals_workspace_bytes(problem, res["depth_var"] is not None)
+    if nb == 0:
+        raise capi.BanetError("ba_marginals: unsupported shape (K <= 256 and P <= 304)")
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, dev)
+    capi.check(L.banet_ba_marginals_f32(ctypes.byref(lv), pA, pD, pS, ctypes.byref(c), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                        capi.stream()))
+    return Marginals(**res)
+
+
 RESIDUAL_GRAD_OUTPUTS = ("dsrc", "dtgt", "ddepth", "dbasis", "dWc", "dR", "dT")
-ResidualGrad = collections.namedtuple("ResidualGrad", RESIDUAL_GRAD_OUTPUTS)
+ResidualGrad =collections.namedtuple("ResidualGrad", RESIDUAL_GRAD_OUTPUTS)
 
 
 def _residual_grad_shapes(problem):

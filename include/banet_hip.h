@@ -293,6 +293,45 @@ int banet_ba_residual_grad_f32(const banet_level_t* lv, const float* R, const fl
                                const banet_residual_grad_in_t* g, const banet_residual_grad_out_t* out,
                                int flags, void* ws, size_t workspace_bytes, banet_stream_t stream);
 
+/* (3d) posterior marginals: how well the normal equations determine their answer.  From the normal matrix AtA [B,P,P] of (3)
+ *     (P = 6 max(pairs, 1) + K, parameter order [pose_1 .. pose_pairs, depth]; only the lower triangle is read), per window b with
+ *     mu = damping[b] (damping == NULL: 0) and s2 = sigma2[b] (sigma2 == NULL: 1):
+ *         H = AtA[b] + mu diag(diag(AtA[b]) + 1e-5)         Sigma = s2 H^-1         H = L L^T
+ *     The damping has the form of bundlenet.py:264-266, but -- UNLIKE the bundle solve of (4), which leaves the last coefficient
+ *     undamped -- it is applied to EVERY diagonal entry, the last one included.
+ *       pose_cov[b]  = the leading 6 pairs x 6 pairs block of Sigma: the joint marginal of all poses with the depth coefficients
+ *                      marginalised out; written exactly symmetric
+ *       wfactor[b]   = T = L_WW^-1, L_WW the trailing K x K block of L, so that Sigma_WW = s2 T^T T (the depth block comes last:
+ *                      marginalising the poses costs nothing); lower triangular, the strict upper triangle written as zeros
+ *       depth_var[b,n] = s2 |T basis[b,n,:]|^2: the variance of D_n = depth + basis . Wc under Sigma; non-negative by construction
+ *       logdet[b]    = log det H = 2 sum_i log L_ii
+ *       status[b]    = 0, or 1 where the factorisation met a pivot <= 0 or a non-finite value (H not positive definite): that
+ *                      window gets depth_var = +inf everywhere, pose_cov = +inf on the diagonal and 0 elsewhere, wfactor = 0,
+ *                      logdet = -inf; the other windows of the batch are unaffected.
+ *     Two launches: a factorisation kernel (one workgroup per window: Cholesky and L^-1 by forward substitution, in float64 on
+ *     the float32 inputs, outputs rounded once -- a float32 factorisation would lose cond(H) 2^-24 of every output; the matrix
+ *     in LDS up to P = 199, in the workspace above) and, when depth_var is asked for, one pass over the basis on the f32-input
+ *     matrix instructions (every product an exact float32 fma; one read of the basis, 4 bytes written per pixel).
+ *     The entry reads lv->B, N, K, pairs and basis and NOTHING else of the level (N and basis only for depth_var), so a level with
+ *     only those fields set is a valid argument.  BANET_ERR_INVALID_ARG, decided before any launch: NULL lv / AtA / out /
+ *     out->pose_cov / out->status; B < 1 (or a negative K / pairs); with depth_var given and K > 0: basis == NULL or N < 1.
+ *     K > 256 or P > 304: workspace_bytes = 0 and BANET_ERR_UNSUPPORTED.  Workspace: required (the scratch contract at the top of
+ *     this file; the query is never 0 for a supported shape), size by the query (want_depth_var = whether out->depth_var will be
+ *     given); NULL, misaligned or too small: BANET_ERR_WORKSPACE.  Enqueue only: no allocation, no synchronisation, no global
+ *     state, one stream.  No float atomics; every summation order depends on N, K and pairs, never on B: a window's bits are the
+ *     same alone and in any batch; a subset of the optional outputs gives the same bits for that subset.  BANET_VERSION is
+ *     unchanged by this addition: detect the entry by its symbol.                                                              */
+typedef struct banet_marginals_out {
+  float* pose_cov;   /* [B][6 pairs][6 pairs]  required */
+  float* depth_var;  /* [B][N]        or NULL; ignored when K == 0 */
+  float* wfactor;    /* [B][K][K]     or NULL; lower-triangular T; ignored when K == 0 */
+  float* logdet;     /* [B]           or NULL: log det H */
+  int32_t* status;   /* [B]           required: 0 = ok, 1 = H not positive definite */
+} banet_marginals_out_t;
+size_t banet_ba_marginals_workspace_bytes(const banet_level_t* lv, int want_depth_var);
+int banet_ba_marginals_f32(const banet_level_t* lv, const float* AtA, const float* damping, const float* sigma2,
+                           const banet_marginals_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream);
+
 /* (4) lambda prediction + damping + solve + SE(3)/W update for all B windows
  *     (bundlenet.py:165-190,241-276; legacy/ba.py:187-213,266-302).  Consumes the outputs
  *     of (3); updates `st` in place.  l2_base: bundlenet.py:252-253 (pass 1.0 for none). */

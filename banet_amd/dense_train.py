@@ -573,13 +573,16 @@ class _SparseIteration(torch.autograd.Function):
 def sparse_iteration_supported(conv1, conv2, Bs, D=None, R=None, T=None):
     """what the fused sparse node accepts (adjoint.hip): float32 CUDA tensors on ONE device, C <= 256, K <= 256, not C > 128 together
     with K > 128, a [f|gx|gy] map of at least 4 x 4 texels (the gather plans refuse smaller ones: the caller falls back to the lean
-    torch graph instead of raising)"""
+    torch graph instead of raising); no odd C or K above 128 -- the node's FORWARD is banet_ba_assemble_f32, whose generic gather kernel
+    is compiled for one channel / coefficient per lane up to 128 and two per lane up to 256 (csrc/gather.hip, launch_c / launch_k:
+    BANET_ERR_UNSUPPORTED otherwise), although the adjoint takes those shapes"""
     C = conv1.shape[-1]
     K = 0 if Bs is None else Bs.shape[-1]
     tensors = [t for t in (conv1, conv2, Bs, D, R, T) if torch.is_tensor(t)]
     same = all(t.is_cuda and t.device == conv1.device and t.dtype == torch.float32 for t in tensors)
+    forward_ok = not (C > 128 and C % 2) and not (K > 128 and K % 2)
     return (same and conv2.dim() == 4 and conv2.shape[1] >= 4 and conv2.shape[2] >= 4 and 1 <= C <= 256 and K <= 256 and
-            not (C > 128 and K > 128) and conv2.shape[-1] == 3 * C)
+            not (C > 128 and K > 128) and forward_ok and conv2.shape[-1] == 3 * C)
 
 
 def sparse_iteration(variant, mlp, l2_base, conv1, conv2, D, Bs, R, T, W, fx, fy, ox, oy, p, layers):

@@ -268,13 +268,13 @@ def _bilinear_sparse(conv2, px, py):
             tap(y0 + 1, x0 + 1) * ax * ay)
 
 
-def sparse_iteration(conv1, conv2, D, Bs, R, T, Wc, lw, bundle, l2, fx, fy, ox, oy, p):
-    """bundlenet.py:122-278 on N sampled points -- BundleIteration (bundle = True) or the pose-only CameraIteration -- every statement
-    a differentiable torch expression in the dtype of its inputs (float64 in the tests): the twin of banet_oracle.bundle_iteration /
-    camera_iteration (pinned to it in tests/test_torch_ref_cpu.py), written with this module's own helpers only.
-    conv1 [B,N,C], conv2 [B,H,W,3C] = [f|gx|gy], D [B,N,1], Bs [B,N,K] or None, R [B,3,3], T [B,3,1], Wc [B,K,1] or None, lw five
-    (filters, biases) pairs, p [B,3,N], fx .. oy [B,N].  -> (R', T', W' or None)"""
-    C, N = conv1.shape[-1], conv1.shape[1]
+def sparse_assemble(conv1, conv2, D, Bs, R, T, Wc, bundle, fx, fy, ox, oy, p):
+    """The assembly statements of bundlenet.py:122-278 on N sampled points -- everything before avg, the lambda MLP and the solve --
+    every statement a differentiable torch expression in the dtype of its inputs: the float64 statement the sparse-layout adjoint
+    kernels are measured against (autograd through it, tests/adjoint_cases.py).  Bs / Wc are None for the pose-only form
+    (bundle = False).  Shapes as sparse_iteration.
+    -> dict(AtA [B,P,P], Atb [B,P], absd [B,C] = sum_n |d|, mask [B,N] (0 / 1), px, py [B,N], d [B,N,C] (masked))"""
+    C = conv1.shape[-1]
     dt = conv1.dtype
     fx8, fy8, ox8, oy8, p8 = fx.to(dt), fy.to(dt), ox.to(dt), oy.to(dt), p.to(dt)
     Dd = D + torch.matmul(Bs, Wc) if bundle else D                                     # :206
@@ -290,11 +290,6 @@ def sparse_iteration(conv1, conv2, D, Bs, R, T, Wc, lw, bundle, l2, fx, fy, ox, 
     d = (conv1 - samp[..., :C]) * m[..., None]
     gx, gy = samp[..., C:2 * C] * m[..., None], samp[..., 2 * C:] * m[..., None]
     M11, M12, M22, g1, g2 = (gx * gx).sum(-1), (gx * gy).sum(-1), (gy * gy).sum(-1), (gx * d).sum(-1), (gy * d).sum(-1)
-    avg = (d.abs().sum(dim=1) / float(N)).unsqueeze(1)
-    y_ = lambda_mlp(avg, lw)
-    lam = torch.sqrt((avg * avg).sum(-1, keepdim=True)) ** (2.0 + y_)
-    if bundle:
-        lam = l2 * lam
     # bundlenet.py:49-61 (CameraJacobianMatrix, with its leading minus), one row per residual component
     iz = 1.0 / Z
     zero = torch.zeros_like(x)
@@ -304,7 +299,6 @@ def sparse_iteration(conv1, conv2, D, Bs, R, T, Wc, lw, bundle, l2, fx, fy, ox, 
     MJ1 = M12.unsqueeze(-1) * J0 + M22.unsqueeze(-1) * J1
     Hcc = torch.matmul(J0.transpose(1, 2), MJ0) + torch.matmul(J1.transpose(1, 2), MJ1)
     bc = (J0 * g1.unsqueeze(-1) + J1 * g2.unsqueeze(-1)).sum(dim=1)
-    nb = conv1.shape[0]
     if bundle:
         jd0 = fx8 * ((rx - rz * x) * iz)                                              # :63-74 (DepthJacobianMatrix)
         jd1 = fy8 * ((ry - rz * y) * iz)
@@ -315,12 +309,31 @@ def sparse_iteration(conv1, conv2, D, Bs, R, T, Wc, lw, bundle, l2, fx, fy, ox, 
         Hdd = torch.matmul(Bs.transpose(1, 2), Bs * s_.unsqueeze(-1))
         bd = torch.matmul(Bs.transpose(1, 2), r.unsqueeze(-1)).squeeze(-1)
         AtA = torch.cat([torch.cat([Hcc, Hcd], dim=2), torch.cat([Hcd.transpose(1, 2), Hdd], dim=2)], dim=1)
-        Atb = torch.cat([bc, bd], dim=1).unsqueeze(-1)
-        diag = torch.diagonal(AtA, dim1=1, dim2=2)
+        Atb = torch.cat([bc, bd], dim=1)
+    else:
+        AtA, Atb = Hcc, bc
+    return dict(AtA=AtA, Atb=Atb, absd=d.abs().sum(dim=1), mask=m, px=px, py=py, d=d)
+
+
+def sparse_iteration(conv1, conv2, D, Bs, R, T, Wc, lw, bundle, l2, fx, fy, ox, oy, p):
+    """bundlenet.py:122-278 on N sampled points -- BundleIteration (bundle = True) or the pose-only CameraIteration -- every statement
+    a differentiable torch expression in the dtype of its inputs (float64 in the tests): the twin of banet_oracle.bundle_iteration /
+    camera_iteration (pinned to it in tests/test_torch_ref_cpu.py), written with this module's own helpers only.
+    conv1 [B,N,C], conv2 [B,H,W,3C] = [f|gx|gy], D [B,N,1], Bs [B,N,K] or None, R [B,3,3], T [B,3,1], Wc [B,K,1] or None, lw five
+    (filters, biases) pairs, p [B,3,N], fx .. oy [B,N].  -> (R', T', W' or None)"""
+    N = conv1.shape[1]
+    a = sparse_assemble(conv1, conv2, D, Bs, R, T, Wc, bundle, fx, fy, ox, oy, p)
+    AtA, Atb = a["AtA"], a["Atb"].unsqueeze(-1)
+    avg = (a["absd"] / float(N)).unsqueeze(1)
+    y_ = lambda_mlp(avg, lw)
+    lam = torch.sqrt((avg * avg).sum(-1, keepdim=True)) ** (2.0 + y_)
+    nb = conv1.shape[0]
+    diag = torch.diagonal(AtA, dim1=1, dim2=2)
+    if bundle:
+        lam = l2 * lam
         damp = torch.cat([diag[:, :-1] + 1e-5, torch.zeros(nb, 1, device=diag.device, dtype=diag.dtype)], dim=-1)     # :264-266
     else:
-        AtA, Atb = Hcc, bc.unsqueeze(-1)
-        damp = torch.diagonal(AtA, dim1=1, dim2=2) + 1e-5                             # :181-182
+        damp = diag + 1e-5                                                            # :181-182
     sol = torch.linalg.solve(AtA + torch.diag_embed(damp * lam.squeeze(-1)), Atb)
     Rw, V = _rodrigues(sol[:, 0:3, 0])
     return torch.matmul(Rw, R), torch.matmul(V, sol[:, 3:6]) + torch.matmul(Rw, T), (Wc + sol[:, 6:]) if bundle else None

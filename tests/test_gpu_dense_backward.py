@@ -65,7 +65,13 @@ def _run_adjoint(intr, lv, R, T, Wc, G, gb, gabs, variant="bundle", overwrite=Fa
 
 @pytest.mark.parametrize("H,W,C,K,seed", [(24, 32, 6, 5, 3), (48, 64, 128, 128, 7), (30, 41, 70, 33, 11), (9, 11, 3, 1, 5),
                                           (16, 16, 64, 16, 2), (17, 33, 130, 40, 9), (20, 24, 256, 64, 4), (15, 21, 128, 128, 6),
-                                          (9, 7, 16, 8, 8)])
+                                          (9, 7, 16, 8, 8),
+                                          # adj_pixel_kernel<1..4, 2> (K = 65 .. 128 that the two-pixel kernel does not take)
+                                          (16, 20, 6, 100, 21), (16, 20, 70, 100, 22), (16, 20, 130, 72, 23), (16, 20, 256, 128, 34),
+                                          # adj_pixel2_kernel: one live lane (C = 4 / K = 4), C / K multiples of 4 but not of 16
+                                          (16, 20, 4, 4, 25), (15, 19, 100, 36, 26), (16, 20, 128, 4, 27), (16, 20, 4, 128, 28),
+                                          # adj_basis6_kernel<5 / 6 / 7 / 2>
+                                          (16, 20, 64, 80, 33), (17, 21, 16, 96, 30), (16, 20, 128, 112, 31), (13, 17, 20, 24, 32)])
 def test_dense_adjoint_kernels_match_the_float64_statement(H, W, C, K, seed):
     intr, levels, R, T, Wc, rng = _scene(H, W, C, K, seed)
     lv = levels[0]
@@ -299,7 +305,9 @@ def _avoid_abs_kinks(intr, lv, R, T, Wc, camera=False):
 
 
 @pytest.mark.parametrize("H,W,C,K,seed", [(20, 24, 8, 136, 3), (20, 24, 128, 256, 5), (18, 22, 70, 200, 7), (16, 20, 256, 192, 9),
-                                          (17, 19, 12, 255, 4), (16, 20, 200, 192, 9), (16, 20, 130, 192, 9), (16, 20, 66, 250, 9)])
+                                          (17, 19, 12, 255, 4), (16, 20, 200, 192, 9), (16, 20, 130, 192, 9), (16, 20, 66, 250, 9),
+                                          # adj_pixel_kernel<2, 3>, <3, 4>, <4, 4> (C = K = 256: the most per-lane state)
+                                          (16, 20, 70, 136, 33), (16, 20, 130, 250, 12), (16, 20, 256, 256, 13)])
 def test_dense_adjoint_kernels_with_more_than_128_depth_coefficients(H, W, C, K, seed):
     """Round 3: 128 < K <= 256 (cfg-5's K = 256) -- the seed block of the GEMM-shaped piece no longer fits the LDS and is taken
     in column chunks (adj_basis_wide_kernel), the per-pixel kernel runs with 3-4 coefficients per lane."""
@@ -477,7 +485,7 @@ def test_solve_differentiable_with_200_depth_coefficients_matches_oracle_finite_
 
 @pytest.mark.parametrize("H,W,C,K,variant", [(24, 32, 128, 128, "bundle"), (17, 33, 130, 40, "bundle"), (20, 24, 256, 64, "bundle"),
                                              (16, 20, 128, 256, "bundle"), (9, 11, 3, 1, "bundle"), (24, 32, 128, 0, "bundle_camera"),
-                                             (21, 27, 6, 0, "bundle_camera")])
+                                             (21, 27, 6, 0, "bundle_camera"), (16, 20, 70, 100, "bundle"), (16, 20, 256, 256, "bundle")])
 def test_dense_adjoint_overwrite_mode_equals_accumulation_into_zeros(H, W, C, K, variant):
     """BANET_ADJOINT_OVERWRITE (banet_dense_adjoint_ex_f32): on NaN-filled buffers the call writes every entry of dsrc / dmap3 /
     ddepth / dbasis -- zeros where nothing contributes -- with the bits the accumulating call leaves in zero-filled buffers.  One

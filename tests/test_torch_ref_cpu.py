@@ -171,3 +171,31 @@ def test_sparse_iteration_twin_matches_the_numpy_oracle():
                                             tt(fx), tt(fy), tt(ox), tt(oy), tt(p))
     np.testing.assert_allclose(rc.numpy(), Rc, rtol=1e-8, atol=1e-10)
     np.testing.assert_allclose(tc.numpy(), Tc, rtol=1e-8, atol=1e-10)
+
+
+def test_sparse_assemble_matches_the_numpy_oracle_with_per_point_intrinsics():
+    """oracle/torch_port.sparse_assemble (the statement the sparse-layout adjoint kernels are differentiated against) gives the
+    AtA / Atb of banet_oracle.bundle_iteration / bundle_camera_iteration to 1e-12 when fx != fy and all four intrinsics differ
+    from point to point and from window to window."""
+    from oracle import torch_port
+    rng = np.random.RandomState(11)
+    B, N, C, K, H, W = 2, 120, 5, 4, 14, 18
+    pts = np.stack([rng.uniform(-0.1 * W, 1.1 * W, (B, N)), rng.uniform(-0.1 * H, 1.1 * H, (B, N))], axis=-1)
+    fx, fy = (0.7 + 0.3 * rng.uniform(size=(B, N))) * W, (0.6 + 0.3 * rng.uniform(size=(B, N))) * W
+    ox, oy = W / 2 + 2 * rng.standard_normal((B, N)), H / 2 + 2 * rng.standard_normal((B, N))
+    p = orc.compute_coordinates(pts, fx, fy, ox, oy, True)
+    conv1, conv2 = rng.standard_normal((B, N, C)), rng.standard_normal((B, H, W, 3 * C))
+    D, Bs = 2.5 + rng.uniform(size=(B, N, 1)), rng.standard_normal((B, N, K)) / K ** 0.5
+    R = np.stack([synth.rodrigues(0.004 * rng.standard_normal(3)) for _ in range(B)])
+    T, Wc = 0.02 * rng.standard_normal((B, 3, 1)), 0.01 * rng.standard_normal((B, K, 1))
+    mlp = orc.he_normal_mlp_weights(C, 4, np.float64)
+    tt = lambda x: torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64)))  # noqa: E731
+    _, _, _, dbg = orc.bundle_iteration(conv1, conv2, fx, fy, ox, oy, p, D, Bs, R, T, Wc, mlp, 1000.0)
+    assert (0 < dbg["mask"].reshape(B, N).sum(1)).all() and (dbg["mask"].reshape(B, N).sum(1) < N).all()
+    a = torch_port.sparse_assemble(tt(conv1), tt(conv2), tt(D), tt(Bs), tt(R), tt(T), tt(Wc), True, tt(fx), tt(fy), tt(ox), tt(oy), tt(p))
+    _, _, dbc = orc.bundle_camera_iteration(conv1, conv2, fx, fy, ox, oy, p, D, R, T, mlp)
+    c = torch_port.sparse_assemble(tt(conv1), tt(conv2), tt(D), None, tt(R), tt(T), None, False, tt(fx), tt(fy), tt(ox), tt(oy), tt(p))
+    for got, want in ((a["AtA"], dbg["AtA"]), (a["Atb"], dbg["Atb"]), (c["AtA"], dbc["AtA"]), (c["Atb"], dbc["Atb"])):
+        want = np.asarray(want).reshape(got.shape)
+        assert np.abs(got.numpy() - want).max() <= 1e-12 * np.abs(want).max()
+    assert np.array_equal(a["mask"].numpy() > 0, np.asarray(dbg["mask"]).reshape(B, N) > 0)

@@ -1,5 +1,5 @@
 // Every bit of banet_level_t.flags that a source of libbanet_hip.so consults, named once.  Plain C++: the host-only plans
-// (plan.hpp), the kernels and the CPU tests (tests/native/plan_host.cpp) read the same names; banet_amd/_capi.py repeats
+// (plan.hpp, adjoint_plan.hpp), the kernels and the CPU tests (tests/native/plan_host.cpp) read the same names; banet_amd/_capi.py repeats
 // them for Python and tests/test_plan_cpu.py compares the two.  0 in production.  The seven public bits are the
 // BANET_FLAG_* values of include/banet_hip.h; the others are development switches (A/B experiments, parity tests,
 // tools/prof_assemble.py) with no promise of stability.
@@ -38,7 +38,7 @@ enum DevFlags : unsigned {
   kDevSolveLdltOnly = 1u << 23,      // solve: blocked LDL^T only, no conjugate gradients (A/B and parity tests)
   kDevSyrkF16 = BANET_FLAG_SYRK_F16,                      // bit 24: the fp16 two-piece SYRK also in a single assembly pass and at any launch size
   kDevForceQuadGather = BANET_FLAG_FORCE_QUAD_GATHER,     // bit 25: the 4x4-pixel-item kernel at any size (parity tests, A/B)
-  // ---- dense adjoint (adjoint.hip) ----
+  // ---- dense adjoint (read by its plan, adjoint_plan.hpp; kernels: adjoint_seed / _pixel / _map.hip) ----
   kDevAdjFp32Mfma = 1u << 26,        // the fp32-MFMA kernel instead of the bf16x6 form of the GEMM-shaped piece (A/B)
   kDevAdjPixelPerWave = 1u << 27,    // one pixel per wave (A/B)
   kDevAdjTexelPerWave = 1u << 28,    // target-map kernel: one texel per wave (A/B)

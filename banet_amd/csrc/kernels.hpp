@@ -179,7 +179,8 @@ int launch_sample_stats_grad(const float* conv1, const float* conv2, const float
                              int H, int W, const float* dstats, const float* dabs, float* dconv1, float* dconv2, float* dpos,
                              hipStream_t s);
 
-// ---- adjoint.hip: backward of the fused dense bundle assembly ----
+// ---- adjoint.hip (driver; plan: adjoint_plan.hpp, kernels: adjoint_*.hip): backward of the fused dense bundle assembly;
+//      the deterministic sample-stats gradient lives in sstats.hip, the target-map fold in adjoint_map.hip ----
 size_t dense_adjoint_workspace_bytes(const banet_level_t* lv, int flags = 0);   // flags: BANET_ADJOINT_FOLD_TARGET changes the layout
 int launch_dense_adjoint(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const float* gAtA,
                          const float* gAtb, const float* gabs, float* dsrc, float* dmap3, float* ddepth, float* dbasis,

@@ -501,7 +501,7 @@ class _SparseIteration(torch.autograd.Function):
     single autograd node on the fused kernels:
       forward   banet_ba_assemble_f32 (gather + SYRK + reduce) and banet_ba_solve_update_f32 -- the inference path, 4-5 launches;
       backward  the small step (lambda MLP, damping, solve by implicit differentiation, SE(3) / W update: _small_step, as the dense
-                path's) and banet_dense_adjoint_f32 on the sparse level (adjoint.hip, adj_pixel_kernel<.., SP = true>): gradients
+                path's) and banet_dense_adjoint_f32 on the sparse level (adjoint_pixel.hip, adj_pixel_kernel<.., SP = true>): gradients
                 of conv1, the [f|gx|gy] map, D, the basis, R, T, W and the lambda weights.  No samp / diff / grad / J tensors, no
                 float atomics (the map adjoint is gathered per texel in a fixed order): bit-reproducible.
     fx / fy / ox / oy / p are data (bundlenet.py:112-120 computes them from the sampled points): no gradient."""
@@ -571,7 +571,7 @@ class _SparseIteration(torch.autograd.Function):
 
 
 def sparse_iteration_supported(conv1, conv2, Bs, D=None, R=None, T=None):
-    """what the fused sparse node accepts (adjoint.hip): float32 CUDA tensors on ONE device, C <= 256, K <= 256, not C > 128 together
+    """what the fused sparse node accepts (plan_adjoint, csrc/adjoint_plan.hpp): float32 CUDA tensors on ONE device, C <= 256, K <= 256, not C > 128 together
     with K > 128, a [f|gx|gy] map of at least 4 x 4 texels (the gather plans refuse smaller ones: the caller falls back to the lean
     torch graph instead of raising); no odd C or K above 128 -- the node's FORWARD is banet_ba_assemble_f32, whose generic gather kernel
     is compiled for one channel / coefficient per lane up to 128 and two per lane up to 256 (csrc/gather.hip, launch_c / launch_k:

@@ -570,7 +570,7 @@ int banet_dense_adjoint_f32(const banet_level_t* lv, const float* R, const float
  *     is not called: 3C (N + HW) floats less memory per window, about a third of the backward's traffic.  The workspace layout
  *     differs: size it with banet_dense_adjoint_workspace_bytes_ex(lv, flags) (0 = unsupported: a window's H W C must stay below 2^30,
  *     the tile kernels use 32-bit byte offsets inside a window).  BANET_ADJOINT_TILE_SHAPE(k), k = 1 .. 13: development
- *     switch (A/B) -- the tile kernel and its tile shape (csrc/adjoint.hip::launch_adj_tile); 0 = the default.                                              */
+ *     switch (A/B) -- the tile kernel and its tile shape (csrc/adjoint_plan.hpp: choose_adj_tile and its shape lists); 0 = the default.                    */
 /*   BANET_ADJOINT_REUSE_DEPTH_SEED (multi-frame windows: the calls for target frames 2 .. of one iteration): the caller states that
  *     the depth block of gAtA, the depth part of gAtb, lv->basis and the workspace are those of the PREVIOUS call -- then z2 = 2 S_dd b,
  *     zeta = b.S_dd b and e = gAtb_d.b of that call are still in the workspace and only the frame's q = S_cd b is computed (one

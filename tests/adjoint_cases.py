@@ -1,5 +1,6 @@
-"""Inputs and float64 references for the kernel-level tests of the SPARSE-layout assembly adjoint (csrc/adjoint.hip:
-adj_pixel_kernel<CJ, KJ, SP = true> and the seed-GEMM / cell-scan / per-texel gather kernels around it), one generator shared by
+"""Inputs and float64 references for the kernel-level tests of the SPARSE-layout assembly adjoint (csrc/adjoint.hip and the
+adjoint_*.hip files behind it: adj_pixel_kernel<CJ, KJ, SP = true> and the seed-GEMM / cell-scan / per-texel gather kernels around
+it), one generator shared by
 the CPU module (test_adjoint_cases_cpu.py: the conditions on the inputs, the float32 yardstick, the dispatch coverage) and the GPU
 module (test_gpu_sparse_adjoint.py).  No GPU here: torch + the oracle only.
 
@@ -16,9 +17,17 @@ mask jump at integer coordinates, |d| has a kink at 0: a point whose float64 pro
 ox / oy moved by 0.01 (repeated until none is left), a masked-in |d| below 1e-5 gets its source feature moved by 1e-3 -- so that a
 float32 and a float64 evaluation never land on different sides.
 """
+import atexit
 import collections
+import ctypes
 import functools
+import os
+import re
+import shutil
+import subprocess
+import tempfile
 
+import numpy as np
 import torch
 
 from oracle import torch_port
@@ -219,55 +228,102 @@ def gate_of(name, output):
     return GATE[output]
 
 
-# ---- the dispatch of launch_dense_adjoint, mirrored ---------------------------------------------------------------------------
-DEV_ADJ_FP32_MFMA, DEV_ADJ_PIXEL_PER_WAVE, DEV_ADJ_TEXEL_PER_WAVE = 1 << 26, 1 << 27, 1 << 28     # csrc/dev_flags.hpp:42-44
+# ---- the dispatch of launch_dense_adjoint, asked of its plan ------------------------------------------------------------------
+# csrc/adjoint_plan.hpp is compiled with g++ (tests/native/adjoint_plan_host.cpp, no ROCm): plan_adjoint itself says what a level
+# launches, and the instantiation lists are its X-macro lists.  Built on first use, once per process.
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+ADJOINT_OVERWRITE, ADJOINT_FOLD_TARGET = 1, 4                     # banet_hip.h: BANET_ADJOINT_OVERWRITE, BANET_ADJOINT_FOLD_TARGET
+BUNDLE_CAMERA, BUNDLE = 2, 3                                      # banet_hip.h: BANET_BUNDLE_CAMERA, BANET_BUNDLE
+
+
+def build_host_lib(out_dir):
+    """compiled exactly as test_plan_cpu.build_host_lib compiles plan_host.cpp"""
+    out = os.path.join(str(out_dir), "libadjoint_plan_host.so")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", out,
+                           os.path.join(ROOT, "tests", "native", "adjoint_plan_host.cpp")])
+    L = ctypes.CDLL(out)
+    for fn in ("banet_test_adjoint_plan_fields", "banet_test_adjoint_instantiations", "banet_test_sstats_det_plan_fields"):
+        getattr(L, fn).restype = ctypes.c_char_p
+    L.banet_test_adjoint_plan_sweep.restype = ctypes.c_size_t
+    L.banet_test_adjoint_plan_sweep.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+    return L
+
+
+@functools.lru_cache(maxsize=None)
+def host_lib():
+    tmp = tempfile.mkdtemp(prefix="banet_adjoint_plan_")
+    atexit.register(shutil.rmtree, tmp, True)
+    return build_host_lib(tmp)
+
+
+def plan_fields(L=None):
+    head, *names = (L or host_lib()).banet_test_adjoint_plan_fields().decode().split()
+    assert head == "desc_ints=12"
+    return names
+
+
+def plan_sweep(desc, L=None):
+    """desc: int32 [n, 12] rows of B, N, C, K, H, W, dense, tgt_has_grad, pairs, variant, level flags, adjoint flags
+    -> (int64 [n, fields] plans, [(seed, pixel, map, tile)] kernel names per row, None where nothing is launched)"""
+    L = L or host_lib()
+    desc = np.ascontiguousarray(desc, np.int32).reshape(-1, 12)
+    out = np.zeros((len(desc), len(plan_fields(L))), np.int64)
+    need = L.banet_test_adjoint_plan_sweep(desc.ctypes.data, len(desc), None, None, 0)
+    buf = ctypes.create_string_buffer(need)
+    L.banet_test_adjoint_plan_sweep(desc.ctypes.data, len(desc), out.ctypes.data, buf, need)
+    lines = buf.value.decode().split("\n")[:len(desc)]
+    names = [tuple(k or None for k in ln.split("|")) if ln else (None,) * 4 for ln in lines]
+    return out, names
+
+
+@functools.lru_cache(maxsize=None)
+def _from_the_lists():
+    """the module constants that are read from the code: the X-macro lists of adjoint_plan.hpp and three names of dev_flags.hpp"""
+    by = collections.defaultdict(list)
+    for ln in host_lib().banet_test_adjoint_instantiations().decode().split("\n"):
+        if ln:
+            kind, name = ln.split("=")
+            by[kind].append(name)
+    pair = lambda n: tuple(int(v) for v in re.match(r"adj_pixel_kernel<(\d+), (\d+)", n).groups())     # noqa: E731
+    import test_plan_cpu                                             # the existing banet_test_dev_flags path
+    tmp = tempfile.mkdtemp(prefix="banet_plan_")
+    atexit.register(shutil.rmtree, tmp, True)
+    flags = test_plan_cpu.dev_flags(test_plan_cpu.build_host_lib(tmp))
+    return dict(SPARSE_POINT_INSTANTIATIONS=tuple(pair(n) for n in by["point"]), DENSE_PIXEL_INSTANTIATIONS=tuple(pair(n) for n in by["pixel"]),
+                # (the <NK, true> twins of adj_basis6_kernel run for target frames 2.. of a multi-frame window only: not a seed CLASS)
+                ALL_SEED_KERNELS=[n for n in by["seed"] if not n.endswith(", true>") and
+                                  not (n.startswith("adj_basis_kernel<") and n != "adj_basis_kernel<1>")],
+                ALL_MAP_KERNELS=by["map"], ALL_TILE_KERNELS=by["tile2"] + by["tile"], ALL_INSTANTIATIONS=dict(by),
+                DEV_ADJ_FP32_MFMA=flags["kDevAdjFp32Mfma"], DEV_ADJ_PIXEL_PER_WAVE=flags["kDevAdjPixelPerWave"],
+                DEV_ADJ_TEXEL_PER_WAVE=flags["kDevAdjTexelPerWave"])
+
+
+def __getattr__(name):                                              # SPARSE_POINT_INSTANTIATIONS, ..., DEV_ADJ_*: built on first use
+    if name.isupper() and name in _from_the_lists():
+        return _from_the_lists()[name]
+    raise AttributeError(name)
+
+
+def level_row(layout, variant, C, K, lv_flags=0, N=0, B=1, adj_flags=0, HW=None):
+    """one row of plan_sweep for a level of the `layout`: dense levels are N x 1 maps (or HW = (H, W)), sparse ones look at 8 x 8"""
+    assert layout in ("dense", "sparse") and (variant == "bundle") == (K > 0)
+    dense = layout == "dense"
+    N = N or 64
+    H, W = HW if HW else ((N, 1) if dense else (8, 8))
+    return (B, H * W if dense else N, C, K, H, W, int(dense), int(not dense), 1, BUNDLE if K > 0 else BUNDLE_CAMERA, lv_flags, adj_flags)
 
 
 def dispatch(layout, variant, C, K, overwrite=False, lv_flags=0, N=0):
     """-> (seed-GEMM kernel, per-pixel kernel, map kernel): the instantiations banet_dense_adjoint_ex_f32 launches for a level of the
     `layout` ("dense" / "sparse") without BANET_ADJOINT_FOLD_TARGET and without BANET_ADJOINT_REUSE_DEPTH_SEED (the <NK, true> twins of
-    adj_basis6_kernel: target frames 2.. of a multi-frame window only).  None where nothing is launched.  Copied from
-    csrc/adjoint.hip, the line ranges next to each piece; N only enters through the 32-bit offset limits of adj_pixel2_kernel."""
-    assert layout in ("dense", "sparse") and (variant == "bundle") == (K > 0)
-    # adjoint.hip:2489-2509   switch ((K + 15) / 16) { case 1: basis<1>; case 2..8: b6 ? basis6<NK> : basis<NK>; 9..12: wide<12>;
-    #                         13..16: wide<16>; case 0: memset }
-    b6 = not (lv_flags & DEV_ADJ_FP32_MFMA)
-    nk = (K + 15) // 16
-    if nk == 0:
-        seed = None
-    elif nk == 1:
-        seed = "adj_basis_kernel<1>"
-    elif nk <= 8:
-        seed = "adj_basis6_kernel<%d, false>" % nk if b6 else "adj_basis_kernel<%d>" % nk
-    elif nk <= 12:
-        seed = "adj_basis_wide_kernel<12, 6>"
-    elif nk <= 16:
-        seed = "adj_basis_wide_kernel<16, 6>"
-    else:
-        raise ValueError("K > 256")
-    # adjoint.hip:2510-2556   if (!lv->dense) BANET_ADJ_POINT(cj, kj) x 12; else if (C % 4 == 0 && K % 4 == 0 && C <= 128 && K <= 128 &&
-    #                         !kDevAdjPixelPerWave && N 3C < 2^30 && N < 2^24) adj_pixel2_kernel<1, overwrite>; else BANET_ADJ_PIXEL x 16
-    cj, kj = (C + 63) // 64, max(1, (K + 63) // 64)
-    if layout == "sparse":
-        pixel = "adj_pixel_kernel<%d, %d, true>" % (cj, kj) if (cj, kj) in SPARSE_POINT_INSTANTIATIONS else None
-    elif (C % 4 == 0 and K % 4 == 0 and C <= 128 and K <= 128 and not (lv_flags & DEV_ADJ_PIXEL_PER_WAVE) and N * 3 * C < (1 << 30) and
-          N < (1 << 24)):
-        pixel = "adj_pixel2_kernel<1, %s>" % ("true" if overwrite else "false")
-    else:
-        pixel = "adj_pixel_kernel<%d, %d>" % (cj, kj) if (cj <= 4 and kj <= 4) else None
-    # adjoint.hip:2272-2291   launch_adj_map: J3 = (3C + 63) / 64; half = 3C % 4 == 0 && !kDevAdjTexelPerWave;
-    #                         J3 <= 3: map2<2, 3> / map<3>; J3 <= 6: map2<3, 6> / map<6>; else map2<6, 12> / map<12>
-    j3 = (3 * C + 63) // 64
-    half = (3 * C) % 4 == 0 and not (lv_flags & DEV_ADJ_TEXEL_PER_WAVE)
-    a, b = (2, 3) if j3 <= 3 else ((3, 6) if j3 <= 6 else (6, 12))
-    mapk = "adj_map2_kernel<%d, %d>" % (a, b) if half else "adj_map_kernel<%d>" % b
-    return seed, pixel, mapk
+    adj_basis6_kernel: target frames 2.. of a multi-frame window only).  None where nothing is launched; a refused level launches
+    nothing.  N only enters through the 32-bit offset limits of adj_pixel2_kernel."""
+    _, names = plan_sweep([level_row(layout, variant, C, K, lv_flags, N, adj_flags=ADJOINT_OVERWRITE if overwrite else 0)])
+    return names[0][:3]
 
 
-# adjoint.hip:2515-2526 (BANET_ADJ_POINT) and :2539-2554 (BANET_ADJ_PIXEL)
-SPARSE_POINT_INSTANTIATIONS = ((1, 1), (2, 1), (3, 1), (4, 1), (1, 2), (2, 2), (3, 2), (4, 2), (1, 3), (2, 3), (1, 4), (2, 4))
-DENSE_PIXEL_INSTANTIATIONS = tuple((c, k) for k in (1, 2, 3, 4) for c in (1, 2, 3, 4))
-ALL_SEED_KERNELS = (["adj_basis_kernel<1>"] + ["adj_basis6_kernel<%d, false>" % nk for nk in range(2, 9)] +
-                    ["adj_basis_wide_kernel<12, 6>", "adj_basis_wide_kernel<16, 6>"])
-ALL_MAP_KERNELS = ["adj_map2_kernel<2, 3>", "adj_map_kernel<3>", "adj_map2_kernel<3, 6>", "adj_map_kernel<6>", "adj_map2_kernel<6, 12>",
-                   "adj_map_kernel<12>"]
+def tile_dispatch(C, shape=0, K=16, HW=(9, 11)):
+    """-> the tile kernel of a dense level with BANET_ADJOINT_FOLD_TARGET | BANET_ADJOINT_TILE_SHAPE(shape)"""
+    _, names = plan_sweep([level_row("dense", "bundle", C, K, adj_flags=ADJOINT_FOLD_TARGET | (shape & 15) << 4, HW=HW)])
+    assert names[0][2] is None                                      # fold mode: no per-texel gather
+    return names[0][3]

@@ -1,13 +1,18 @@
 """The inputs of the sparse-layout adjoint tests (adjoint_cases.py) are what they claim to be, the float32 yardstick the GPU module
-(test_gpu_sparse_adjoint.py) relies on, the dispatch of launch_dense_adjoint enumerated against the cases of both adjoint GPU modules,
-and the shapes the sparse layout refuses -- all on the CPU.
+(test_gpu_sparse_adjoint.py) relies on, the dispatch of launch_dense_adjoint -- asked of its own plan, csrc/adjoint_plan.hpp compiled
+with g++ -- enumerated against the cases of both adjoint GPU modules, the plan's workspace totals against the loaded library, and
+the shapes the sparse layout refuses -- all on the CPU.
 
 The yardstick: the same autograd through oracle/torch_port.sparse_assemble in float32 torch against float64, on the same float32
 inputs, every tensor on its own per-window max-norm scale.  It must stay below a quarter of the gate: the gate is then reachable by
 plain float32 arithmetic and the inputs are not ill-posed."""
 import ctypes
+import hashlib
+import json
 import os
+import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -107,35 +112,7 @@ def test_window_errors_does_not_let_a_wrong_window_hide():
     assert ac.window_errors(got, want)[0] == float("inf")
 
 
-# ---- the dispatch mirror ---------------------------------------------------------------------------------------------------------
-def _mirror_matches_the_source():
-    """the line ranges adjoint_cases.dispatch cites still hold what it copies"""
-    lines = open(os.path.join(ROOT, "banet_amd", "csrc", "adjoint.hip")).read().split("\n")
-    seg = lambda lo, hi: "\n".join(lines[lo - 1:hi])             # noqa: E731
-    return seg(2489, 2509), seg(2510, 2556), seg(2272, 2291)
-
-
-def test_dispatch_mirror_cites_the_lines_it_copies():
-    seed, pixel, mapk = _mirror_matches_the_source()
-    assert seed.lstrip().startswith("const bool b6") and "switch ((K + 15) / 16)" in seed and seed.rstrip().endswith("}")
-    for nk in range(2, 9):
-        assert "case %d: b6 ? launch_adj_basis6<%d>(a, pl.Ga, s) : launch_adj_basis<%d>(a, pl.Ga, s); break;" % (nk, nk, nk) in seed
-    assert "case 1: launch_adj_basis<1>" in seed and "case 9: case 10: case 11: case 12: launch_adj_basis_wide<12>" in seed
-    assert "case 13: case 14: case 15: case 16: launch_adj_basis_wide<16>" in seed
-    assert pixel.lstrip().startswith("if (!lv->dense)") and pixel.rstrip().endswith("}")
-    point = [l for l in pixel.split("\n") if l.strip().startswith("BANET_ADJ_POINT(")]
-    dense = [l for l in pixel.split("\n") if l.strip().startswith("BANET_ADJ_PIXEL(")]
-    assert [tuple(int(v) for v in l.strip()[16:-2].split(",")) for l in point] == list(ac.SPARSE_POINT_INSTANTIATIONS)
-    assert [tuple(int(v) for v in l.strip()[16:-2].split(",")) for l in dense] == list(ac.DENSE_PIXEL_INSTANTIATIONS)
-    assert "(lv->C & 3) == 0 && (K & 3) == 0 && lv->C <= 128 && K <= 128 && !(lv->flags & kDevAdjPixelPerWave)" in pixel
-    assert "adj_pixel2_kernel<1, true>" in pixel and "adj_pixel2_kernel<1, false>" in pixel
-    assert mapk.startswith("static void launch_adj_map") and mapk.rstrip().endswith("}")
-    for k in ac.ALL_MAP_KERNELS:
-        assert k in mapk, k
-    flags = open(os.path.join(ROOT, "banet_amd", "csrc", "dev_flags.hpp")).read()
-    assert "kDevAdjFp32Mfma = 1u << 26" in flags and "kDevAdjPixelPerWave = 1u << 27" in flags and "kDevAdjTexelPerWave = 1u << 28" in flags
-
-
+# ---- the dispatch, answered by plan_adjoint (csrc/adjoint_plan.hpp through tests/native/adjoint_plan_host.cpp) -------------------
 def test_dispatch_mirror_on_known_shapes():
     assert ac.dispatch("dense", "bundle", 128, 128, True) == ("adj_basis6_kernel<8, false>", "adj_pixel2_kernel<1, true>", "adj_map2_kernel<3, 6>")
     assert ac.dispatch("dense", "bundle", 128, 128, False)[1] == "adj_pixel2_kernel<1, false>"
@@ -145,9 +122,117 @@ def test_dispatch_mirror_on_known_shapes():
     assert ac.dispatch("dense", "bundle", 128, 128, False, N=1 << 24)[1] == "adj_pixel_kernel<2, 2>"
     assert ac.dispatch("sparse", "bundle", 128, 128, True) == ("adj_basis6_kernel<8, false>", "adj_pixel_kernel<2, 2, true>", "adj_map2_kernel<3, 6>")
     assert ac.dispatch("sparse", "bundle_camera", 131, 0, True) == (None, "adj_pixel_kernel<3, 1, true>", "adj_map_kernel<12>")
-    assert ac.dispatch("sparse", "bundle", 130, 130, True)[1] is None            # refused before the launch (adj_supported)
+    assert ac.dispatch("sparse", "bundle", 130, 130, True)[1] is None            # refused before the launch (no point instantiation)
     assert ac.dispatch("dense", "bundle", 3, 1) == ("adj_basis_kernel<1>", "adj_pixel_kernel<1, 1>", "adj_map_kernel<3>")
     assert ac.dispatch("dense", "bundle", 256, 256)[:2] == ("adj_basis_wide_kernel<16, 6>", "adj_pixel_kernel<4, 4>")
+
+
+def test_fold_mode_tile_dispatch_on_known_shapes():
+    """BANET_ADJOINT_FOLD_TARGET: (channel chunks, vector width) by C, tile shape by BANET_ADJOINT_TILE_SHAPE"""
+    assert ac.tile_dispatch(128, 0) == "adj_tile2_kernel<8, 4>"
+    assert [ac.tile_dispatch(128, k) for k in range(9, 14)] == ["adj_tile2_kernel<8, 3>", "adj_tile2_kernel<8, 5>", "adj_tile2_kernel<8, 7>",
+                                                                "adj_tile2_kernel<16, 3>", "adj_tile2_kernel<16, 2>"]
+    assert ac.tile_dispatch(128, 3) == "adj_tile_kernel<1, 2, 8, 2>"
+    assert ac.tile_dispatch(6) == "adj_tile_kernel<1, 2, 8, 4>"
+    assert ac.tile_dispatch(131) == "adj_tile_kernel<4, 1, 8, 4>"
+    for shape in range(8, 16):                                   # C = 130 has no two-visit kernel: a shape >= 8 is shape 0 of adj_tile_kernel
+        assert ac.tile_dispatch(130, shape) == "adj_tile_kernel<2, 2, 8, 4>"
+    assert ac.tile_dispatch(5) == "adj_tile_kernel<1, 1, 8, 4>"
+    # every tile instantiation of the lists is some level's choice, and no level chooses another
+    got = {ac.tile_dispatch(C, k) for C in (5, 6, 65, 128, 130, 131) for k in range(16)}
+    assert got == set(ac.ALL_TILE_KERNELS)
+
+
+# ---- the plan against the loaded library: the header the tests compile and the library cannot drift ----------------------------
+SWEEP_DENSE_HW = ((4, 4), (9, 11), (48, 64), (480, 640))
+SWEEP_SPARSE_N = (1, 65, 4096)
+SWEEP_C, SWEEP_K, SWEEP_B = (3, 4, 128, 131, 256), (0, 1, 16, 40, 128, 130, 256), (1, 2, 32)
+SWEEP_ADJ_FLAGS = (0,) + tuple(ac.ADJOINT_FOLD_TARGET | k << 4 for k in range(14))      # every layout-changing flag: fold off / on, tile shapes 0-13
+
+
+def workspace_sweep_rows():
+    """plan_sweep rows: dense H x W and sparse N (looking at a 20 x 24 map) x C x K x B x adjoint flags"""
+    rows = []
+    for C in SWEEP_C:
+        for K in SWEEP_K:
+            for B in SWEEP_B:
+                for fl in SWEEP_ADJ_FLAGS:
+                    var = "bundle" if K else "bundle_camera"
+                    rows += [ac.level_row("dense", var, C, K, B=B, adj_flags=fl, HW=hw) for hw in SWEEP_DENSE_HW]
+                    rows += [ac.level_row("sparse", var, C, K, N=N, B=B, adj_flags=fl, HW=(20, 24)) for N in SWEEP_SPARSE_N]
+    return rows
+
+
+def library_workspace_bytes(L, rows):
+    """banet_dense_adjoint_workspace_bytes_ex of the loaded library for plan_sweep rows (host side, no launch)"""
+    from banet_amd import _capi as capi
+    one = (ctypes.c_float * 4)()
+    ptr = ctypes.cast(one, ctypes.c_void_p).value                # any non-null pointer: the plan only checks presence
+    out = []
+    for B, N, C, K, H, W, dense, grad, pairs, variant, lv_flags, adj_flags in rows:
+        lv = capi.Level()
+        lv.B, lv.N, lv.C, lv.K, lv.H, lv.W = B, N, C, K, H, W
+        lv.variant, lv.dense, lv.tgt_has_grad, lv.scale, lv.pairs, lv.flags = variant, dense, grad, 1.0, pairs, lv_flags
+        lv.src = lv.tgt = lv.depth = lv.basis = lv.rays = lv.fx = lv.fy = lv.ox = lv.oy = ptr
+        out.append(L.banet_dense_adjoint_workspace_bytes_ex(ctypes.byref(lv), adj_flags))
+    return out
+
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "adjoint_plan_digests.json")
+
+
+def plan_digests():
+    """what the golden file keeps: SHA-256 over (rc, every AdjPlan field) as int64 and over the chosen kernels' names, of the workspace
+    sweep and of its unfolded rows once more under each of the three kDevAdj* switches and with BANET_ADJOINT_OVERWRITE"""
+    rows = workspace_sweep_rows()
+    plain = [r for r in rows if r[11] == 0]
+    for bit in (ac.DEV_ADJ_FP32_MFMA, ac.DEV_ADJ_PIXEL_PER_WAVE, ac.DEV_ADJ_TEXEL_PER_WAVE):
+        rows += [r[:10] + (bit, 0) for r in plain]
+    rows += [r[:11] + (ac.ADJOINT_OVERWRITE,) for r in plain]
+    plans, names = ac.plan_sweep(rows)
+    text = "\n".join("|".join(k or "" for k in row) for row in names)
+    return {"what": "tests/test_adjoint_cases_cpu.py: SHA-256 of the plan_adjoint sweep (PYTHONPATH=. python tests/test_adjoint_cases_cpu.py --regenerate)",
+            "cases": len(rows), "fields": ac.plan_fields(), "plans_sha256": hashlib.sha256(plans.tobytes()).hexdigest(),
+            "kernels_sha256": hashlib.sha256(text.encode()).hexdigest()}
+
+
+def test_adjoint_plans_match_the_recorded_digests():
+    """a changed G is a changed summation tree, a changed offset is two buffers overlapping, a changed kernel choice is other arithmetic:
+    none may happen silently.  After a DELIBERATE change: PYTHONPATH=. python tests/test_adjoint_cases_cpu.py --regenerate"""
+    assert plan_digests() == json.load(open(GOLDEN))
+
+
+SSTATS_SWEEP = [(B, N, C, H, W) for B in SWEEP_B for N in SWEEP_SPARSE_N for C in SWEEP_C + (257,) for H, W in SWEEP_DENSE_HW]
+
+
+def test_plan_bytes_equal_the_library_workspace_queries():
+    from banet_amd import _capi as capi
+    L = capi.lib()
+    rows = workspace_sweep_rows()
+    plans, _ = ac.plan_sweep(rows)
+    col = {n: i for i, n in enumerate(ac.plan_fields())}
+    want = [int(p[col["bytes"]]) if p[col["rc"]] == 0 else 0 for p in plans]
+    got = library_workspace_bytes(L, rows)
+    bad = [(r, g, w) for r, g, w in zip(rows, got, want) if g != w]
+    assert not bad, "%d of %d differ, first: %s" % (len(bad), len(rows), bad[0])
+    assert 0 in want and sum(1 for w in want if w > 0) > len(want) // 2          # refusals and plans both met
+    ok = plans[plans[:, col["rc"]] == 0]
+    refused = plans[plans[:, col["rc"]] != 0]
+    assert len(refused) and (np.delete(refused, col["rc"], axis=1) == 0).all()      # a refused plan carries no layout and no kernel
+    for f in [n for n in col if n.startswith("off_")] + ["bytes"]:
+        assert (ok[:, col[f]] % 256 == 0).all(), f
+    # the deterministic sample-stats gradient (its entry refuses B H W 3C >= 2^32 itself, before the plan)
+    host = ac.host_lib()
+    head, *names = host.banet_test_sstats_det_plan_fields().decode().split()
+    assert head == "desc_ints=5"
+    desc = np.ascontiguousarray(SSTATS_SWEEP, np.int32)
+    out = np.zeros((len(desc), len(names)), np.int64)
+    host.banet_test_sstats_det_plan_sweep(desc.ctypes.data_as(ctypes.c_void_p), len(desc), out.ctypes.data_as(ctypes.c_void_p))
+    rc, nbytes = names.index("rc"), names.index("bytes")
+    for (B, N, C, H, W), p in zip(SSTATS_SWEEP, out):
+        want = int(p[nbytes]) if p[rc] == 0 and B * H * W * 3 * C < (1 << 32) else 0
+        assert L.banet_sample_stats_grad_workspace_bytes(B, N, C, H, W) == want, (B, N, C, H, W)
+        assert (C > 256) == (p[rc] != 0)
 
 
 def _params(fn):
@@ -230,3 +315,12 @@ def test_sparse_layout_refusals():
     assert ws(pairs=2) == 0
     for c in ac.CASES:                                           # every case of the GPU module is accepted
         assert ws(C=c.C, K=max(c.K, 1)) > 0, c.name
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--regenerate"]:
+        sys.exit("usage: PYTHONPATH=. python tests/test_adjoint_cases_cpu.py --regenerate   (rewrites tests/golden/adjoint_plan_digests.json from the current tree)")
+    with open(GOLDEN, "w") as f:
+        json.dump(plan_digests(), f, indent=1)
+        f.write("\n")
+    print("wrote", GOLDEN)

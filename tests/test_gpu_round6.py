@@ -1,4 +1,4 @@
-"""Round 6 (`-m gpu`, through the C ABI): the backward's target-tile kernel (BANET_ADJOINT_FOLD_TARGET, adjoint.hip::adj_tile_kernel:
+"""Round 6 (`-m gpu`, through the C ABI): the backward's target-tile kernel (BANET_ADJOINT_FOLD_TARGET, adjoint_tile.hip::adj_tile_kernel:
 the target map's gradient accumulated per 8x8 texel tile in LDS -- no 3C adjoint rows, no [f|gx|gy] map adjoint, no fold pass)
 against the float64 statement of the adjoint (oracle/dense_adjoint.py) and against the round-5 path (rows + per-texel gather +
 banet_target_map_adjoint_f32), bit-reproducibility, overwrite == accumulate-into-zeros, windows with most / all pixels masked,

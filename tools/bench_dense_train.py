@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Training step of the dense BA layer: DenseBA.solve_differentiable (fused forward kernels, fused backward kernels of
-csrc/adjoint.hip) -- forward-only solve vs forward + backward, per-kernel share of the backward, peak memory; and, at a size
+csrc/adjoint.hip and the adjoint_*.hip files behind it) -- forward-only solve vs forward + backward, per-kernel share of the backward, peak memory; and, at a size
 the reference-layout graph can hold, the same step through BundleNet's lean training graph (ops.sample_stats + torch) on all
 pixels as points.   python tools/bench_dense_train.py [B] [H] [W] [iters]"""
 import os, sys, time

@@ -8,7 +8,7 @@ import collections, os, re, sys
 f = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r06_run4_backward_sq_counters.txt")
 v = collections.defaultdict(dict)
 for line in open(f):
-    m = re.match(r"void banet::\(anonymous namespace\)::(adj_\w+)<([^>]*)>.*?\s(\w+)\s+launches=\s*(\d+)\s+mean=([0-9.e+]+)", line)
+    m = re.match(r"void banet::(?:adj::)?\(anonymous namespace\)::(adj_\w+)<([^>]*)>.*?\s(\w+)\s+launches=\s*(\d+)\s+mean=([0-9.e+]+)", line)
     if m:
         v[m.group(1) + "<" + m.group(2) + ">"][m.group(3)] = float(m.group(5))
 for k, c in v.items():

@@ -138,7 +138,17 @@ class MarginalsOut(ctypes.Structure):
     _fields_ = [("pose_cov", _FP), ("depth_var", _FP), ("wfactor", _FP), ("logdet", _FP), ("status", _FP)]
 
 
-ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2   # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
+class ReprojectOut(ctypes.Structure):
+    """mirror of banet_reproject_out_t (banet_depth_reproject_f32: both required)"""
+    _fields_ = [("depth", _FP), ("index", _FP)]
+
+
+class BasisFitOut(ctypes.Structure):
+    """mirror of banet_basis_fit_out_t (banet_basis_fit_f32: Wc and status required, the others optional)"""
+    _fields_ = [("Wc", _FP), ("normal", _FP), ("rhs", _FP), ("stats", _FP), ("status", _FP)]
+
+
+ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2  # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
 
 EXPORTS = {
     "banet_version": (ctypes.c_int, []),
@@ -168,6 +178,10 @@ EXPORTS = {
                                                   ctypes.c_int, _FP, ctypes.c_size_t, _FP]),
     "banet_ba_marginals_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.c_int]),
     "banet_ba_marginals_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(MarginalsOut), _FP, ctypes.c_size_t, _FP]),
+    "banet_depth_reproject_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),
+    "banet_depth_reproject_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(ReprojectOut), _FP, ctypes.c_size_t, _FP]),
+    "banet_basis_fit_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),
+    "banet_basis_fit_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(BasisFitOut), _FP, ctypes.c_size_t, _FP]),
     "banet_ba_solve_update_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float] + [_FP] * 4 +
                                   [ctypes.POINTER(State), _FP]),
     "banet_ba_solve_update_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),

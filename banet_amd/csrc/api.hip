@@ -340,6 +340,40 @@ int banet_ba_marginals_f32(const banet_level_t* lv, const float* AtA, const floa
   return launch_marginals(lv, pl, AtA, damping, sigma2, out, ws, static_cast<hipStream_t>(stream));
 }
 
+size_t banet_depth_reproject_workspace_bytes(const banet_level_t* lv) {
+  size_t bytes = 0;
+  if (plan_reproject(lv, &bytes) != BANET_OK) return 0;
+  return bytes;
+}
+
+int banet_depth_reproject_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc,
+                              const banet_reproject_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream) {
+  if (!lv || !R || !T || !out || !out->depth || !out->index) return BANET_ERR_INVALID_ARG;
+  size_t bytes = 0;
+  const int rc = plan_reproject(lv, &bytes);
+  if (rc != BANET_OK) return rc;
+  if (!lv->depth || !lv->intr || (lv->K > 0 && Wc && !lv->basis)) return BANET_ERR_INVALID_ARG;
+  if (!ws || workspace_bytes < bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
+  return launch_reproject(lv, R, T, Wc, out, ws, static_cast<hipStream_t>(stream));
+}
+
+size_t banet_basis_fit_workspace_bytes(const banet_level_t* lv) {
+  FitPlan pl;
+  if (plan_basis_fit(lv, &pl) != BANET_OK) return 0;
+  return pl.bytes;
+}
+
+int banet_basis_fit_f32(const banet_level_t* lv, const float* target, const float* weight, const float* damping,
+                        const banet_basis_fit_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream) {
+  if (!lv || !target || !out || !out->Wc || !out->status) return BANET_ERR_INVALID_ARG;
+  FitPlan pl;
+  const int rc = plan_basis_fit(lv, &pl);
+  if (rc != BANET_OK) return rc;
+  if (!lv->depth || !lv->basis) return BANET_ERR_INVALID_ARG;
+  if (!ws || workspace_bytes < pl.bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
+  return launch_basis_fit(lv, pl, target, weight, damping, out, ws, static_cast<hipStream_t>(stream));
+}
+
 int banet_ba_solve_update_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, const float* AtA,
                               const float* Atb, const float* absres, const float* nvalid, banet_state_t* st,
                               banet_stream_t stream) {

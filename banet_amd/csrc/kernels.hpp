@@ -90,6 +90,28 @@ int plan_marginals(const banet_level_t* lv, int want_depth_var, MargPlan* pl);
 int launch_marginals(const banet_level_t* lv, const MargPlan& pl, const float* AtA, const float* damping, const float* sigma2,
                      const banet_marginals_out_t* out, void* ws, hipStream_t s);
 
+// ---- reproject.hip: the key frame's depth map in the target frames' pixel grids, z-buffered (banet_depth_reproject_f32) ----
+// reads lv->B / N / K / H / W / dense / scale / pairs only; BANET_ERR_INVALID_ARG (NULL, a non-positive size, N != H W, scale <= 0)
+// or BANET_ERR_UNSUPPORTED (a sparse level); *bytes = the 64-bit keys [B][max(pairs, 1)][H][W]
+int plan_reproject(const banet_level_t* lv, size_t* bytes);
+int launch_reproject(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_reproject_out_t* out,
+                     void* ws, hipStream_t s);
+
+// ---- basisfit.hip: weighted, damped least squares of a depth map on a level's basis (banet_basis_fit_f32) ----
+constexpr int kFitKMax = 256;
+struct FitPlan {    // the workspace of one call; host memory only
+  int K, NR, NP;    // NR 32-column blocks, NP = NR (NR + 1) / 2 lower 32 x 32 blocks of G
+  int chunk, rows;  // pixels per partial row, partial rows per window: functions of N alone
+  int pstride;      // floats per partial row
+  bool big;         // the solve kernel's matrix (packed lower triangle, doubles) lives in the workspace (K >= 200)
+  size_t lds;       // the solve kernel's dynamic LDS
+  size_t off_part, off_G, off_g, off_big, bytes;
+};
+// reads lv->B / N / K only; BANET_ERR_INVALID_ARG (NULL, B < 1) or BANET_ERR_UNSUPPORTED (K outside 1 .. 256, N < 1)
+int plan_basis_fit(const banet_level_t* lv, FitPlan* pl);
+int launch_basis_fit(const banet_level_t* lv, const FitPlan& pl, const float* target, const float* weight, const float* damping,
+                     const banet_basis_fit_out_t* out, void* ws, hipStream_t s);
+
 // ---- prep.hip --------------------------------------------------------------------------
 int launch_resample(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,
                     hipStream_t s);

@@ -15,6 +15,7 @@ import torch
 from . import ops
 
 DenseMarginals = collections.namedtuple("DenseMarginals", "pose_cov depth_var wfactor logdet status sigma2 damping")
+DepthTransfer = collections.namedtuple("DepthTransfer", "Wc depth_map index covered status")
 
 
 class DenseLevel:
@@ -241,6 +242,39 @@ class DenseBA:
         dv = m.depth_var.reshape(p.B, int(p.c.H), int(p.c.W)) if m.depth_var is not None else None
         as_t = lambda v: v if (v is None or torch.is_tensor(v)) else torch.full((p.B,), float(v), dtype=torch.float32, device=p.device)
         return DenseMarginals(m.pose_cov, dv, m.wfactor, m.logdet, m.status, as_t(sigma2), as_t(damping))
+
+    transfer_eps = 1e-6    # transfer_depth: weight = covered / (depth_var + transfer_eps)
+
+    def transfer_depth(self, level_index, state, new_depth, new_basis, frame=0, depth_var=None, damping=1e-3):
+        """Carry the solved depth of level `level_index` over to a new key frame: target frame `frame` of the window.
+          1. ops.depth_reproject at `state` (an LmState): the key frame's depth + basis . Wc in frame `frame`'s pixel grid, z-buffered;
+          2. weights: 1 on the covered texels (index >= 0), 0 elsewhere; with depth_var [B,H,W] (DenseBA.marginals(...).depth_var, the
+             variance per key-frame pixel) covered / (depth_var gathered by index + transfer_eps);
+          3. ops.basis_fit of that map on the new key frame's new_depth [B,H,W] and new_basis [B,H,W,K'] (the level's H, W), damped.
+        -> DepthTransfer(Wc [B,K'] = the new key frame's coefficients, depth_map [B,H,W], index [B,H,W] int32, covered [B] = the number
+        of covered texels, status [B] int32 as ops.basis_fit).  Five launches plus the weights' torch plumbing; no host sync and no
+        autograd (the result is detached from any graph)."""
+        p = self.problems[level_index]
+        B, H, W = p.B, int(p.c.H), int(p.c.W)
+        if not 0 <= int(frame) < p.pairs:
+            raise ops.capi.BanetError("DenseBA.transfer_depth: frame %d of a window with %d target frames" % (frame, p.pairs))
+        if not (new_depth.is_cuda and new_basis.is_cuda) or (depth_var is not None and not depth_var.is_cuda):
+            raise ops.capi.BanetError("banet_amd runs on the GPU only")
+        if new_depth.numel() != B * H * W or new_basis.dim() != 4 or new_basis.numel() != B * H * W * new_basis.shape[-1]:
+            raise ops.capi.BanetError("DenseBA.transfer_depth: expected new_depth [B,H,W] and new_basis [B,H,W,K'] at the level's %d x %d" % (H, W))
+        with torch.no_grad():
+            rep = ops.depth_reproject(p, state.R, state.T, state.Wc if self.K > 0 else None)
+            depth_map, index = rep.depth[:, frame].contiguous(), rep.index[:, frame].contiguous()
+            hit = index >= 0
+            weight = hit.to(torch.float32)
+            if depth_var is not None:
+                if depth_var.numel() != B * H * W:
+                    raise ops.capi.BanetError("DenseBA.transfer_depth: depth_var must be [B,H,W]")
+                var = torch.gather(depth_var.detach().reshape(B, H * W).float(), 1, index.reshape(B, H * W).clamp(min=0).long())
+                weight = weight / (var.reshape(B, H, W) + self.transfer_eps)
+            fit = ops.basis_fit(new_depth.detach().reshape(B, H * W), new_basis.detach().reshape(B, H * W, -1), depth_map.reshape(B, H * W),
+                                weight=weight.reshape(B, H * W), damping=damping)
+            return DepthTransfer(fit.Wc, depth_map, index, hit.reshape(B, -1).sum(dim=1), fit.status)
 
     def cost_trace(self, snapshots, state0=None):
         """Did each level reduce the cost?  snapshots: what solve(snapshots=...) filled; state0: the state that solve started from

@@ -405,6 +405,91 @@ def ba_marginals(problem, AtA, damping=None, sigma2=None, want=("pose_cov", "dep
     return Marginals(**res)
 
 
+Reprojection = collections.namedtuple("Reprojection", "depth index")
+
+
+def depth_reproject(problem, R, T, Wc=None, ws=None):
+    """banet_depth_reproject_f32: the key frame's depth map depth + basis . Wc (Wc None: depth) of a dense level reprojected into
+    the pixel grid of every target frame at the poses R [B,F,3,3], T [B,F,3,1] (F = max(pairs, 1)), z-buffered ->
+    Reprojection(depth [B,F,H,W] = the depth IN THE TARGET FRAME (range along the ray on normalize_rays levels, else z) of the
+    nearest point that lands on the texel, 0 where nothing lands; index [B,F,H,W] int32 = that point's source pixel, -1 where
+    nothing lands).  Device tensors, no host sync; integer atomics only: bit-reproducible, a window's bits do not depend on the
+    batch."""
+    L = capi.lib()
+    lv = problem.c
+    B, N, K, F = int(lv.B), int(lv.N), int(lv.K), max(int(lv.pairs), 1)
+    H, W = int(lv.H), int(lv.W)
+    R, T = capi.f32c(R), capi.f32c(T)
+    Wc = capi.f32c(Wc) if (Wc is not None and K > 0) else None
+    pR, pT, pW = capi.ptr(R), capi.ptr(T), capi.ptr(Wc)      # (CPU tensors: BanetError, before anything is allocated)
+    if R.numel() != B * F * 9 or T.numel() != B * F * 3 or (Wc is not None and Wc.numel() != B * K):
+        raise capi.BanetError("depth_reproject: expected R [B,F,3,3], T [B,F,3,1], Wc [B,K,1] for B = %d, F = %d, K = %d" % (B, F, K))
+    dev = R.device
+    nb = int(L.banet_depth_reproject_workspace_bytes(ctypes.byref(lv)))
+    if nb == 0:
+        raise capi.BanetError("depth_reproject: a dense level with N = H W is needed")
+    out = Reprojection(torch.empty((B, F, H, W), dtype=torch.float32, device=dev), torch.empty((B, F, H, W), dtype=torch.int32, device=dev))
+    c = capi.ReprojectOut()
+    c.depth, c.index = out.depth.data_ptr(), out.index.data_ptr()
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, dev)
+    capi.check(L.banet_depth_reproject_f32(ctypes.byref(lv), pR, pT, pW, ctypes.byref(c), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                           capi.stream()))
+    return out
+
+
+BASIS_FIT_OUTPUTS = ("Wc", "normal", "rhs", "stats")
+BasisFit = collections.namedtuple("BasisFit", "Wc normal rhs stats status")
+
+
+def basis_fit(depth, basis, target, weight=None, damping=None, want=("Wc",), ws=None):
+    """banet_basis_fit_f32: the weighted, damped least-squares fit of a depth map on a basis.  depth [B,N] (any shape with B
+    leading), basis [B,N,K], target and weight like depth (weight None: 1), damping None (0), a float or a tensor [B].  With
+    r = target - depth over the points with a finite weight > 0 and a finite target:
+        G = sum w b b^T    g = sum w r b    H = G + damping diag(diag(G) + 1e-5)    Wc = H^-1 g
+    -> BasisFit(Wc [B,K], normal [B,K,K] = G (exactly symmetric), rhs [B,K] = g, stats [B,2] = (sum w, sum w r^2), status [B]
+    int32: 0, or 1 where H is not positive definite (that window: Wc = 0)).  `want` names the optional outputs (Wc and status
+    always are); the others are None.  Device tensors, no host sync; a window's bits do not depend on the batch nor on `want`."""
+    L = capi.lib()
+    depth, basis, target = capi.f32c(depth), capi.f32c(basis), capi.f32c(target)
+    weight = capi.f32c(weight) if weight is not None else None
+    pd, pb, pt, pw = capi.ptr(depth), capi.ptr(basis), capi.ptr(target), capi.ptr(weight)   # (CPU tensors: BanetError)
+    B, K = int(basis.shape[0]), int(basis.shape[-1])
+    N = basis.numel() // max(B * K, 1)
+    if depth.numel() != B * N or target.numel() != B * N or (weight is not None and weight.numel() != B * N):
+        raise capi.BanetError("basis_fit: expected depth / target / weight [B,N] and basis [B,N,K] with B = %d, N = %d" % (B, N))
+    unknown = [w for w in want if w not in BASIS_FIT_OUTPUTS]
+    if unknown:
+        raise capi.BanetError("basis_fit: unknown outputs %s" % unknown)
+    dev = basis.device
+    if damping is not None:
+        damping = damping if torch.is_tensor(damping) else torch.full((B,), float(damping), dtype=torch.float32, device=dev)
+        damping = capi.f32c(damping).reshape(-1)
+        if damping.numel() == 1 and B > 1:
+            damping = damping.expand(B).contiguous()
+        if damping.numel() != B:
+            raise capi.BanetError("basis_fit: damping must be a float or hold B = %d values" % B)
+    lv = capi.Level()                                     # a bare level: the entry reads B, N, K, depth and basis only
+    lv.B, lv.N, lv.K = B, N, K
+    lv.depth, lv.basis = pd.value, pb.value
+    nb = int(L.banet_basis_fit_workspace_bytes(ctypes.byref(lv)))
+    if nb == 0:
+        raise capi.BanetError("basis_fit: unsupported shape (1 <= K <= 256, N >= 1)")
+    res = dict(Wc=torch.empty((B, K), dtype=torch.float32, device=dev),
+               normal=torch.empty((B, K, K), dtype=torch.float32, device=dev) if "normal" in want else None,
+               rhs=torch.empty((B, K), dtype=torch.float32, device=dev) if "rhs" in want else None,
+               stats=torch.empty((B, 2), dtype=torch.float32, device=dev) if "stats" in want else None,
+               status=torch.empty((B,), dtype=torch.int32, device=dev))
+    c = capi.BasisFitOut()
+    for name, t in res.items():
+        setattr(c, name, None if t is None else t.data_ptr())
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, dev)
+    capi.check(L.banet_basis_fit_f32(ctypes.byref(lv), pt, pw, capi.ptr(damping), ctypes.byref(c), ctypes.c_void_p(ws.data_ptr()),
+                                     ws.numel(), capi.stream()))
+    return BasisFit(**res)
+
+
 RESIDUAL_GRAD_OUTPUTS = ("dsrc", "dtgt", "ddepth", "dbasis", "dWc", "dR", "dT")
 ResidualGrad =collections.namedtuple("ResidualGrad", RESIDUAL_GRAD_OUTPUTS)
 

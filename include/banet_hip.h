@@ -332,6 +332,68 @@ size_t banet_ba_marginals_workspace_bytes(const banet_level_t* lv, int want_dept
 int banet_ba_marginals_f32(const banet_level_t* lv, const float* AtA, const float* damping, const float* sigma2,
                            const banet_marginals_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream);
 
+/* (3e) depth transfer to a new key frame: what a window learned about the scene, carried into another frame.  Two entries.
+ *   banet_depth_reproject_f32: the key frame's depth map D = depth + basis . Wc (Wc == NULL or K == 0: D = depth) reprojected
+ *     into the pixel grid of every target frame f (F = max(pairs, 1); R [B,F,9], T [B,F,3]) with a z-buffer.  Per source pixel n
+ *     and frame f, by the float32 statements of the assembly pass (3): the ray p_n from the pixel index, the level scale and intr
+ *     (normalised iff normalize_rays), X = R_f (p_n D) + T_f, (px, py) with the level intrinsics intr / scale, and the point's
+ *     depth in the target frame in the level's own convention, d' = |X| if normalize_rays (range along the ray, bundlenet.py:119)
+ *     else X_z (legacy/ba.py:33-34).  The point is valid iff 0 <= px <= W-1 and 0 <= py <= H-1 (the in-image mask of (3); a NaN
+ *     fails it), X_z > 0 and d' is finite and > 0; it lands on texel (floor(px + 0.5), floor(py + 0.5)).  Per texel the winner is
+ *     the landed point with the smallest (bits of d' as uint32, n), lexicographically:
+ *       depth[b,f,y,x] = the winner's d', bit for bit; 0 where nothing lands
+ *       index[b,f,y,x] = the winner's n;               -1 where nothing lands
+ *     Every element of both outputs is written.  No splatting over neighbours: holes under magnification are reported as -1.
+ *     Three launches (key init, splat with an unsigned 64-bit integer atomic min on (d' bits << 32) | n, decode); integer atomics
+ *     only, so the result does not depend on the order in which points arrive: bit-reproducible, and a window's bits are the same
+ *     alone and in any batch.  16-byte loads of the basis rows where K % 4 == 0 and basis is 16-byte aligned, 4-byte loads
+ *     otherwise: the same bits.  Dense levels (dense = 1) of any variant; the entry reads B, N, K, H, W, dense, normalize_rays,
+ *     scale, pairs, depth, basis, intr and NOTHING else of the level (src, tgt and C are not read).  BANET_ERR_INVALID_ARG, decided
+ *     before any launch: NULL lv / R / T / out / out->depth / out->index / lv->depth / lv->intr (lv->basis with K > 0 and Wc
+ *     given), B, N, H or W < 1, a negative K / pairs, N != H W, scale <= 0; dense = 0: BANET_ERR_UNSUPPORTED and a query of 0.
+ *     Workspace: required, B F H W 8 bytes (the keys) rounded up to 256; NULL, misaligned or too small: BANET_ERR_WORKSPACE.
+ *   banet_basis_fit_f32: a weighted, damped least-squares fit of a depth map on a level's basis -- the new key frame's
+ *     coefficients from the reprojected map, or a depth observation (RGB-D, a prior) as normal equations.  Per window b, with
+ *     target, weight [B,N] (weight == NULL: 1), mu = damping[b] (damping == NULL: 0) and r_n = target_n - depth_n, over the points
+ *     with a finite w_n > 0 and a finite target_n (texels of the reprojection with index = -1 go in with w = 0):
+ *         G = sum_n w_n b_n b_n^T     g = sum_n w_n r_n b_n     H = G + mu diag(diag(G) + 1e-5)     Wc = H^-1 g
+ *     (the damping on every diagonal entry, as (3d)).  G and g are exactly what such a depth term adds to the depth block of AtA /
+ *     Atb in front of (4).
+ *       Wc[b]      = the solution; 0 where status = 1
+ *       normal[b]  = G, full and exactly symmetric            rhs[b] = g
+ *       stats[b]   = (sum_n w_n, sum_n w_n r_n^2) over the contributing points
+ *       status[b]  = 0, or 1 where the factorisation met a pivot <= 0 or a non-finite value (H not positive definite): that window
+ *                    gets Wc = 0; the other windows of the batch are unaffected.
+ *     Three launches: the Gram pass (one read of the basis on the f32-input matrix instructions, every product an exact float32
+ *     fma; partial rows per contiguous pixel range in the workspace), a fold that adds the rows in a fixed order, and one
+ *     workgroup per window for the Cholesky factorisation and the two substitutions in float64 on the float32 H, Wc rounded once
+ *     (the matrix in LDS up to K = 199, in the workspace above).  The entry reads lv->B, N, K, depth and basis and NOTHING else of
+ *     the level: a level with only those fields set is a valid argument, sparse N included.  BANET_ERR_INVALID_ARG, decided before
+ *     any launch: NULL lv / target / out / out->Wc / out->status / lv->depth / lv->basis, B < 1.  K outside 1 .. 256 or N < 1:
+ *     workspace_bytes = 0 and BANET_ERR_UNSUPPORTED.  Workspace: required, size by the query; NULL, misaligned or too small:
+ *     BANET_ERR_WORKSPACE.
+ *   Both: enqueue only -- no allocation, no synchronisation, no global state, one stream.  No float atomics; the number of
+ *   partial rows and every summation order depend on N and K only, never on B: a window's bits are the same alone and in any
+ *   batch; a subset of the optional outputs gives the same bits for that subset.  BANET_VERSION is unchanged by this addition:
+ *   detect the entries by their symbols.                                                                                        */
+typedef struct banet_reproject_out {
+  float* depth;    /* [B,F,H,W]  required: depth of the winning point in the TARGET frame, 0 where nothing lands */
+  int32_t* index;  /* [B,F,H,W]  required: the winning source pixel n, -1 where nothing lands */
+} banet_reproject_out_t;
+size_t banet_depth_reproject_workspace_bytes(const banet_level_t* lv);
+int banet_depth_reproject_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc,
+                              const banet_reproject_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream);
+typedef struct banet_basis_fit_out {
+  float* Wc;        /* [B,K]    required */
+  float* normal;    /* [B,K,K]  or NULL: G, full and exactly symmetric */
+  float* rhs;       /* [B,K]    or NULL: g */
+  float* stats;     /* [B,2]    or NULL: sum_n w_n, sum_n w_n r_n^2 */
+  int32_t* status;  /* [B]      required: 0 ok, 1 H not positive definite (that window: Wc = 0; others unaffected) */
+} banet_basis_fit_out_t;
+size_t banet_basis_fit_workspace_bytes(const banet_level_t* lv);
+int banet_basis_fit_f32(const banet_level_t* lv, const float* target, const float* weight, const float* damping,
+                        const banet_basis_fit_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream);
+
 /* (4) lambda prediction + damping + solve + SE(3)/W update for all B windows
  *     (bundlenet.py:165-190,241-276; legacy/ba.py:187-213,266-302).  Consumes the outputs
  *     of (3); updates `st` in place.  l2_base: bundlenet.py:252-253 (pass 1.0 for none). */

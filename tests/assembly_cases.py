@@ -1,0 +1,530 @@
+"""Cases, metric and mutations for the entry-by-entry gate of the forward assembly (gather -> per-pixel records -> SYRK -> AtA, Atb):
+one table shared by the CPU module (test_assembly_cases_cpu.py: the conditions on the inputs, the float32 twin, what the metric sees
+that the max-norm gate does not, the table against plan.hpp) and the GPU module (test_gpu_assembly_entrywise.py).  No GPU here:
+numpy, torch on the CPU, the float64 twin of oracle/torch_port.py.
+
+The metric (as _entry_errors of test_gpu_syrk_f16_pipeline.py): every entry of AtA against sqrt(A_ii A_jj), every entry of Atb against
+sqrt(A_ii) |r|, |r| the 2-norm of the channel sums of |residual| -- reported per block (pose x pose, pose x depth, depth x depth, Atb pose,
+Atb depth), because the blocks differ by decades (largest entry 6e3 .. 7e5 / 9 .. 3e3 / 0.2 .. 400) and the max-norm gate of the other
+modules, max|got - want| / max|want| < 3e-5, only sees the first.
+
+A case: a scene (banet_amd.synth.make_dense_windows on the CPU with a fixed seed, or N sparse points built as
+test_sparse_gather_with_16_point_items_equals_the_64_point_items builds them), a state (small random rotations, 0.7 T_gt,
+Wc ~ 0.004 randn: the depth dot is live), the flag bits of banet_level_t.flags and the (gather, SYRK) selection these must give on the
+256 CUs of an MI355X.  Cases that differ in their flags only share a scene, hence a twin.
+
+How the axes are crossed.  Every (kernel, shape) appears once with a small and once with a large motion, `kernel` being the kernel
+(or forced sub-mode) that runs, not every (K, C, frames) configuration of it:
+  * gather axis: every flag set at all three shapes and both motions; (K, target frames) alternate between the six slots so that each
+    flag set meets K = 20 and K = 128 and one and three target frames, both at a ragged shape under the large motion;
+  * SYRK axis (default gather): the configurations of one kernel form take turns through the six (shape, motion) slots, each
+    configuration at least once with either motion, each form through all six;
+  * sparse layout: every (N, C, K) with both item sizes and both motions.
+"""
+import collections
+import ctypes
+import functools
+
+import numpy as np
+import torch
+
+from oracle import torch_port
+
+GATE = 3e-5                       # every block of every case
+GATE_THREE_PRODUCTS = 1e-4        # the opt-in three-product SYRK: its own documented bound (tests/test_gpu_round3.py:176)
+TWIN32_GATE = 3e-6                # the float32 twin against float64, per block: a tenth of the gate
+ABSRES_GATE = 1e-5
+MASKED_SHARE = 0.05               # large motion: at least this share of every window's and frame's pixels outside the image
+B_WINDOWS = 2
+MI355X_CUS = 256                  # the selections of the table are stated for this part
+BLOCKS = ("pose_pose", "pose_depth", "depth_depth", "atb_pose", "atb_depth")
+
+Case = collections.namedtuple("Case", "name layout H W N C K pairs flags motion seed gather syrk direct f16 gate")
+# layout "dense": H x W pixels, N = H W; "sparse": N points on a 48 x 64 [f|gx|gy] map (tgt_has_grad = 1, what every caller of the
+# sparse layout builds); "sparse_map": the same points on the C-channel map (tgt_has_grad = 0), which at C = 128 sends the sparse
+# layout to ba_gather128_kernel -- accepted by the library, built by no caller, and the combination whose plan counts 16-point items
+# in front of a kernel that indexes by 64.  flags: int, the level's flag word.  gather / syrk: what
+# banet_gather_selection / banet_syrk_selection must return (syrk 4 = an fp16 two-piece form); direct / f16: SyrkPlan.direct / .f16
+# behind that number (the fp16 forms of ba_syrk_bf16x6_kernel and of syrk_wide.hip both report 4).
+
+
+def _flags():
+    from banet_amd import _capi as F
+    return F
+
+
+# ---- shapes, motions, seeds ---------------------------------------------------------------------------------------------------
+# the smallest shapes that are ragged in every work-item size (4x4 items, 8x8 tiles, 16-wide strip segments of 8 / 16 / 32 rows,
+# 32-pixel SYRK steps): W = 21 is the strip gather's minimum width; 48 x 32 is whole items throughout
+SHAPES = ((23, 21), (37, 53), (32, 48))                       # (H, W)
+MOTIONS = {"small": 0.06, "large": 1.0}                       # trans_mag of the scene; the state keeps 0.3 T_gt of it as residual motion
+# Large motion.  A translation t moves the projections by about 0.8 W x 0.7 t / 2.8 = 0.2 W t pixels and its components are uniform in
+# +-trans_mag, so at trans_mag = 0.3 a frame loses 6 % of the image at the very most and a typical one little more than the rim that
+# the small motion already loses: 5 % of EVERY window and frame (up to 14 frames a scene) cannot be had from it.  trans_mag = 1.0
+# leaves 5 .. 60 % outside; the seeds below are the first, counted from the base seed, at which every window and frame has its 5 %,
+# none is empty and no projection is borderline.
+SLOTS = ((0, "small"), (1, "large"), (2, "small"), (0, "large"), (1, "small"), (2, "large"))   # (shape, motion): the motions alternate
+SPARSE_HW = (48, 64)
+# sigma of the translation; the points are drawn past the image's rim, so both motions leave their share outside.  Small: 0.06 like
+# the dense scenes' trans_mag, not the 0.02 of the test the recipe is from -- the depth Jacobian fx (rx - rz x) / Z is a difference of
+# nearly equal numbers when the parallax |T| / D is small, and at 0.02 the float32 twin itself is 3e-6 .. 1e-5 off in the depth block
+# (median 6e-6 over 400 seeds at N = 77): a case on which plain float32 arithmetic does not stay a decade below the gate.
+# (For the same reason the image is low-passed: _low_pass.)
+SPARSE_MOTIONS = {"small": 0.06, "large": 0.15}
+
+SEED_STEP = 1000                  # seed = base + SEED_STEP x attempt
+# scene (without its seed) -> attempt, where the base seed does not meet the conditions of test_assembly_cases_cpu.py: the first that does
+SEED_ATTEMPT = {
+    ("dense", 37, 53, 128, 20, 3, "large"): 1, ("dense", 23, 21, 128, 128, 3, "large"): 9, ("dense", 37, 53, 128, 4, 1, "large"): 1,
+    ("dense", 23, 21, 128, 12, 3, "large"): 3, ("dense", 37, 53, 128, 20, 1, "small"): 7, ("dense", 32, 48, 128, 200, 1, "small"): 1,
+    ("dense", 37, 53, 128, 5, 1, "small"): 2, ("dense", 23, 21, 128, 33, 3, "small"): 1, ("dense", 37, 53, 128, 33, 3, "large"): 2,
+    ("dense", 23, 21, 7, 16, 1, "large"): 1, ("dense", 23, 21, 128, 64, 1, "small"): 2, ("dense", 23, 21, 128, 64, 4, "large"): 4,
+    ("dense", 32, 48, 128, 128, 1, "large"): 1, ("dense", 37, 53, 128, 128, 4, "large"): 1, ("dense", 37, 53, 128, 64, 4, "large"): 2,
+    ("dense", 23, 21, 128, 128, 4, "large"): 1, ("dense", 32, 48, 128, 128, 4, "large"): 2, ("dense", 23, 21, 128, 256, 2, "large"): 1,
+    ("dense", 32, 48, 128, 256, 7, "large"): 4, ("dense", 23, 21, 128, 128, 7, "large"): 14,
+    ("sparse", 77, 128, 128, "large"): 1,
+}
+
+
+def _base_seed(H, W, C, K, pairs, motion):
+    return 7 + H + 3 * W + 5 * (C % 97) + 11 * K + 13 * pairs + (500 if motion == "large" else 0)
+
+
+def scene_key(case):
+    if case.layout == "dense":
+        return ("dense", case.H, case.W, case.C, case.K, case.pairs, case.motion, case.seed)
+    return ("sparse", case.N, case.C, case.K, case.motion, case.seed)          # (both sparse layouts: one scene)
+
+
+# ---- the table ----------------------------------------------------------------------------------------------------------------
+def _dense(group, H, W, C, K, pairs, flags, motion, gather, syrk, direct, f16, gate=GATE, tag=""):
+    key = (H, W, C, K, pairs, motion)
+    seed = _base_seed(*key) + SEED_STEP * SEED_ATTEMPT.get(("dense",) + key, 0)
+    name = "%s%s-%dx%d-C%d-K%d-p%d-%s" % (group, tag, H, W, C, K, pairs, motion)
+    return Case(name, "dense", H, W, H * W, C, K, pairs, int(flags), motion, seed, gather, syrk, direct, f16, gate)
+
+
+def _syrk_sel(K, pairs, no_bf16x6=False, f16=False):
+    """(syrk selection, SyrkPlan.direct, SyrkPlan.f16) as plan_syrk states them"""
+    if K == 0:
+        return -1000, 0, 0
+    direct = 0
+    if K in (64, 128) and pairs <= 4:
+        direct = 1 if no_bf16x6 else 2
+    if not no_bf16x6 and (K == 256 or (K == 128 and pairs > 4)):
+        direct = 3
+    on = int(f16 and direct in (2, 3))
+    return (4 if on else direct), direct, on
+
+
+def gather_flag_sets():
+    """name -> (flag bits, gather selection, frames: None = as the slot says, 3 = multi-frame only)"""
+    F = _flags()
+    strip = F.DEV_FORCE_STRIP_GATHER
+    direct = F.DEV_DIRECT_GATHER | F.DEV_NO_STRIP_GATHER | F.DEV_NO_QUAD_GATHER
+    patch = F.DEV_FORCE_PATCH_GATHER | F.DEV_NO_QUAD_GATHER
+    return collections.OrderedDict([
+        ("generic", (F.DEV_GENERIC_GATHER | F.DEV_NO_QUAD_GATHER, 0, None)),
+        ("direct", (direct, 1, None)),                                 # (the plan's own choice: quarter tiles at these sizes)
+        ("direct_tiles", (direct | F.DEV_NO_QUARTER_TILES, 1, None)),  # whole 8x8 tiles
+        ("direct_quarter", (direct | F.DEV_QUARTER_TILES, 1, None)),
+        ("patch", (patch, 2, None)),
+        ("patch_frameloop", (patch | F.DEV_PATCH_PAIR_LOOP, 2, 3)),
+        ("strip", (strip, 3, None)),                                   # three target frames: the frame-parallel workgroups
+        ("strip_frameparallel", (strip, 3, 3)),                        # ... also in the slots whose frame count is 1
+        ("strip_frameloop", (strip | F.DEV_STRIP_FRAME_LOOP, 3, 3)),
+        ("strip_rows8", (strip | F.DEV_QUARTER_TILES, 3, None)),
+        ("strip_rows32", (strip | F.DEV_STRIP_ROWS32, 3, None)),
+        ("strip_directrows", (strip | F.DEV_STRIP_DIRECT_ROWS, 3, None)),
+        ("quad", (F.DEV_FORCE_QUAD_GATHER, 4, None)),
+    ])
+
+
+# (K, target frames) of the six slots of the gather axis, in SLOTS order: every flag set meets K = 20 / 128 x 1 / 3 frames, one frame
+# at a ragged shape under the large motion (23x21) and three frames at another (37x53)
+GATHER_SLOT_KP = {((23, 21), "small"): (20, 3), ((23, 21), "large"): (128, 1), ((37, 53), "small"): (128, 1),
+                  ((37, 53), "large"): (20, 3), ((32, 48), "small"): (20, 1), ((32, 48), "large"): (128, 3)}
+
+
+def _gather_axis():
+    out = []
+    for name, (bits, sel, frames) in gather_flag_sets().items():
+        for si, motion in SLOTS:
+            H, W = SHAPES[si]
+            K, pairs = GATHER_SLOT_KP[(SHAPES[si], motion)]
+            if frames is not None:
+                if name == "strip_frameparallel" and pairs == frames:
+                    continue                                            # that slot is `strip` itself
+                pairs = frames
+            s, d, f = _syrk_sel(K, pairs)
+            out.append(_dense("gather_" + name, H, W, 128, K, pairs, bits, motion, sel, s, d, f))
+    return out
+
+
+def syrk_forms():
+    """form -> [(tag, C, K, frames, flag bits, expected gather selection)]; the default gather: the 4x4-item kernel at C = 128 with
+    K % 4 == 0 (latency-bound launches), the generic kernel otherwise"""
+    F = _flags()
+    no6, f16, exact = F.DEV_SYRK_NO_BF16X6, F.DEV_SYRK_F16, F.DEV_NO_SYRK_F16
+    forms = collections.OrderedDict()
+    forms["lds"] = ([("", 128, K, p, 0, 4) for K, p in ((4, 1), (12, 3), (20, 1), (36, 3), (200, 1))] +
+                    [("", 128, K, p, 0, 0) for K, p in ((5, 1), (33, 3))] +              # K & 3: the generic gather
+                    [("", 7, 16, 1, 0, 0)] +
+                    [("_nobf16x6", 128, K, 5, no6, 4) for K in (128, 256)])
+    forms["direct"] = [("", 128, K, p, no6, 4) for K in (64, 128) for p in (1, 4)]
+    forms["bf16x6"] = [("", 128, K, 4, 0, 4) for K in (64, 128)]
+    forms["bf16x6_f16"] = [("", 128, K, 4, f16, 4) for K in (64, 128)]
+    wide = [(128, 256, 1), (128, 256, 2), (128, 256, 7), (128, 128, 5), (128, 128, 7), (20, 256, 5)]
+    forms["wide"] = [("", C, K, p, exact, 4 if C == 128 else 0) for C, K, p in wide]
+    forms["wide_f16"] = [("", C, K, p, f16, 4 if C == 128 else 0) for C, K, p in wide]
+    forms["three_products"] = [("", 128, 128, 1, F.DEV_SYRK_THREE_PRODUCTS, 4)]
+    return forms
+
+
+def _syrk_axis():
+    F = _flags()
+    out = []
+    for form, configs in syrk_forms().items():
+        per = max(2, -(-len(SLOTS) // len(configs)))                    # slots per configuration: all six slots per form
+        if form == "three_products":
+            per = 2                                                     # (opt-in, not the product path: one ragged shape, both motions)
+        at = 0
+        for tag, C, K, pairs, bits, gsel in configs:
+            for _ in range(per):
+                si, motion = SLOTS[at % len(SLOTS)]
+                at += 1
+                H, W = SHAPES[si]
+                s, d, f = _syrk_sel(K, pairs, bool(bits & F.DEV_SYRK_NO_BF16X6), bool(bits & F.DEV_SYRK_F16))
+                gate = GATE_THREE_PRODUCTS if form == "three_products" else GATE
+                out.append(_dense("syrk_" + form, H, W, C, K, pairs, bits, motion, gsel, s, d, f, gate, tag))
+    return out
+
+
+SPARSE_NCK = ((77, 128, 0), (77, 128, 128), (1000, 70, 33), (1000, 128, 64))
+
+
+def _sparse_axis():
+    F = _flags()
+    out = []
+    for N, C, K in SPARSE_NCK:
+        for motion in SPARSE_MOTIONS:
+            key = (N, C, K, motion)
+            seed = 2000 * B_WINDOWS + N + K + (500 if motion == "large" else 0) + SEED_STEP * SEED_ATTEMPT.get(("sparse",) + key, 0)
+            for tag, bits in (("items16", 0), ("items64", F.DEV_SPARSE_ITEMS64)):
+                s, d, f = _syrk_sel(K, 1)
+                out.append(Case("sparse_%s-N%d-C%d-K%d-%s" % (tag, N, C, K, motion), "sparse", SPARSE_HW[0], SPARSE_HW[1], N, C, K, 1,
+                                int(bits), motion, seed, 0, s, d, f, GATE))
+                if C == 128 and K and K % 4 == 0:                       # the direct C = 128 kernel on sparse points
+                    out.append(Case("sparsemap_%s-N%d-C%d-K%d-%s" % (tag, N, C, K, motion), "sparse_map", SPARSE_HW[0], SPARSE_HW[1], N,
+                                    C, K, 1, int(bits), motion, seed, 1, s, d, f, GATE))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def all_cases():
+    cases = _gather_axis() + _syrk_axis() + _sparse_axis()
+    assert len({c.name for c in cases}) == len(cases)
+    return tuple(cases)
+
+
+def all_scenes():
+    """one case per distinct scene, in table order"""
+    seen, out = set(), []
+    for c in all_cases():
+        if scene_key(c) not in seen:
+            seen.add(scene_key(c))
+            out.append(c)
+    return out
+
+
+# ---- scenes and states --------------------------------------------------------------------------------------------------------
+def _rodrigues(w):
+    from banet_amd import synth as bsynth
+    return bsynth._rodrigues(w)
+
+
+@functools.lru_cache(maxsize=None)
+def make_scene(key):
+    """the float32 inputs of a scene, on the CPU (nothing downstream writes into them)"""
+    B = B_WINDOWS
+    if key[0] == "dense":
+        from banet_amd import synth as bsynth
+        _, H, W, C, K, pairs, motion, seed = key
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)                                 # (the multi-frame builder draws its noise from the global generator)
+            intr, levels, gt = bsynth.make_dense_windows(B, H, W, C, K, [1], seed, "cpu", trans_mag=MOTIONS[motion], pairs=pairs)
+        lv = levels[0]
+        g = torch.Generator().manual_seed(seed + 1)
+        R = torch.stack([torch.stack([_rodrigues((torch.rand(3, generator=g) * 2 - 1) * 0.003) for _ in range(pairs)]) for _ in range(B)])
+        T = (gt["T"] * 0.7).reshape(B, pairs, 3, 1).float()
+        Wc = torch.randn(B, K, 1, generator=g) * 0.004
+        tgt = lv.tgt if lv.tgt.dim() == 5 else lv.tgt.unsqueeze(1)
+        return dict(layout="dense", B=B, H=H, W=W, N=H * W, C=C, K=K, pairs=pairs, intr=intr, scale=lv.scale, src=lv.src, tgt=tgt,
+                    depth=lv.depth, basis=lv.basis, R=R.contiguous(), T=T.contiguous(), Wc=Wc.contiguous())
+    _, N, C, K, motion, seed = key
+    H, W = SPARSE_HW
+    g = torch.Generator().manual_seed(seed)
+    img = _low_pass(torch.randn(B, H, W, C, generator=g))
+    gx, gy = torch_port.grad_fixed(img)
+    conv2 = torch.cat([img, gx, gy], dim=-1).contiguous()            # the [f|gx|gy] map (tgt_has_grad = 1)
+    pts = torch.stack([torch.rand(B, N, generator=g) * (W + 2) - 1.5, torch.rand(B, N, generator=g) * (H + 2) - 1.5], dim=-1)
+    at = pts.clamp(min=0.0)
+    conv1 = torch_port._bilinear_sparse(img, at[..., 0], at[..., 1]) + 0.05 * torch.randn(B, N, C, generator=g)
+    fx = torch.full((B, N), 0.8 * W)
+    ox, oy = torch.full((B, N), W / 2.0), torch.full((B, N), H / 2.0)
+    ray = torch.stack([(pts[..., 0] - ox) / fx, (pts[..., 1] - oy) / fx, torch.ones(B, N)], dim=1)
+    p = (ray / ray.norm(dim=1, keepdim=True)).contiguous()
+    D = 2.5 + torch.rand(B, N, generator=g)
+    Bs = torch.randn(B, N, K, generator=g) / max(K, 1) ** 0.5 if K else None
+    R = torch.stack([_rodrigues((torch.rand(3, generator=g) * 2 - 1) * 0.003) for _ in range(B)])
+    T = SPARSE_MOTIONS[motion] * torch.randn(B, 3, 1, generator=g)
+    Wc = 0.01 * torch.randn(B, K, 1, generator=g) if K else None
+    return dict(layout="sparse", B=B, H=H, W=W, N=N, C=C, K=K, pairs=1, conv1=conv1.contiguous(), conv2=conv2, img=img, D=D, Bs=Bs, p=p, fx=fx,
+                fy=fx.clone(), ox=ox, oy=oy, R=R.contiguous(), T=T, Wc=Wc)
+
+
+def _low_pass(img):
+    """[B,H,W,C] white noise through the 5-tap binomial filter, twice, back to unit variance.  The white-noise image of the recipe has
+    a gradient of one standard deviation per pixel; the float32 projection is only good to 4e-6 pixels at px ~ 64, which on such an
+    image moves every sample by 4e-6 of its scale -- with the 77-point scenes (few points per sum, nothing averages out) the float32
+    twin itself is then 3e-6 .. 8e-6 off in the depth block.  Low-passed, it stays below 2e-6 at the median."""
+    x = img.permute(0, 3, 1, 2)
+    C = x.shape[1]
+    k = torch.tensor([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
+    k2 = (k[:, None] * k[None, :]).reshape(1, 1, 5, 5).repeat(C, 1, 1, 1)
+    for _ in range(2):
+        x = torch.nn.functional.conv2d(torch.nn.functional.pad(x, (2, 2, 2, 2), mode="reflect"), k2, groups=C)
+    return (x / x.std()).permute(0, 2, 3, 1).contiguous()
+
+
+def scene_of(case):
+    return make_scene(scene_key(case))
+
+
+# ---- the twin -----------------------------------------------------------------------------------------------------------------
+Twin = collections.namedtuple("Twin", "A b absres nvalid mask borderline")
+# per window: A [P,P], b [P], absres [C] float64; nvalid float; mask bool [pairs, N] (the evaluation's OWN mask); borderline int
+
+
+def _np(x):
+    return x.detach().cpu().numpy()
+
+
+def _borderline(px, py, W, H):
+    """as torch_port.assemble_prepared counts them: projections within 4e-6 max(W, H) pixels of the mask's boundary"""
+    e = 4e-6 * max(W, H)
+    inx, iny = (px >= -e) & (px <= W - 1 + e), (py >= -e) & (py <= H - 1 + e)
+    near = (((px.abs() < e) | ((px - (W - 1)).abs() < e)) & iny) | (((py.abs() < e) | ((py - (H - 1)).abs() < e)) & inx)
+    return near.sum(-1)
+
+
+def _twin_of_scene(sc, mask, dtype):
+    B, pairs, N = sc["B"], sc["pairs"], sc["N"]
+    out = []
+    if sc["layout"] == "dense":
+        for b in range(B):                                          # one window at a time
+            sl = slice(b, b + 1)
+            stats = {}
+            mo = None if mask is None else torch.as_tensor(np.asarray(mask)[sl].reshape(1, pairs, N).astype(np.uint8))
+            A, bb, ab, nv = torch_port.window_assemble(sc["intr"][sl], sc["scale"], sc["src"][sl], sc["tgt"][sl], sc["depth"][sl],
+                                                       sc["basis"][sl], sc["R"][sl], sc["T"][sl], sc["Wc"][sl], True, dtype, stats, mo)
+            own = torch.stack(stats["mask"], 1)[0]
+            out.append(Twin(_np(A[0]).astype(np.float64), _np(bb[0]).astype(np.float64), _np(ab[0]).astype(np.float64),
+                            float(nv.sum()), _np(own), int(stats["borderline"][0])))
+        return out
+    assert mask is None, "the sparse statement has no forced mask"
+    c = lambda v: None if v is None else v.to(dtype)              # noqa: E731
+    bundle = sc["K"] > 0
+    a = torch_port.sparse_assemble(c(sc["conv1"]), c(sc["conv2"]), c(sc["D"]).unsqueeze(-1), c(sc["Bs"]), c(sc["R"]), c(sc["T"]),
+                                   c(sc["Wc"]), bundle, c(sc["fx"]), c(sc["fy"]), c(sc["ox"]), c(sc["oy"]), c(sc["p"]))
+    bl = _borderline(a["px"], a["py"], sc["W"], sc["H"])
+    for b in range(B):
+        m = _np(a["mask"][b]) > 0
+        out.append(Twin(_np(a["AtA"][b]).astype(np.float64), _np(a["Atb"][b]).astype(np.float64), _np(a["absd"][b]).astype(np.float64),
+                        float(m.sum()), m.reshape(1, N), int(bl[b])))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _twin_cached(key, mask_bytes, dtype):
+    sc = make_scene(key)
+    mask = None if mask_bytes is None else np.frombuffer(mask_bytes, np.uint8).reshape(sc["B"], sc["pairs"], sc["N"])
+    tw = _twin_of_scene(sc, mask, dtype)
+    for t in tw:
+        for v in t:
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+    return tuple(tw)
+
+
+def twin(case, mask=None, dtype=torch.float64):
+    """the twin of a case, one Twin per window: dense cases oracle/torch_port.window_assemble one window at a time (mask: uint8 / bool
+    [B, pairs, N], evaluated through mask_override), sparse cases torch_port.sparse_assemble (its own mask only).  Shared between the
+    cases of a scene and never written into."""
+    mb = None if mask is None else np.ascontiguousarray(np.asarray(mask) > 0).astype(np.uint8).tobytes()
+    return _twin_cached(scene_key(case), mb, dtype)
+
+
+def own_mask(tw):
+    """uint8 [B, pairs, N] of a twin"""
+    return np.stack([t.mask for t in tw]).astype(np.uint8)
+
+
+# ---- the metric ---------------------------------------------------------------------------------------------------------------
+def entry_errors(AtA, Atb, absres, A64, b64, pairs):
+    """one window.  -> (dict block -> largest scaled error, dict block -> index of that entry in AtA (row, col) resp. Atb (row,)):
+    |AtA - A64| / sqrt(A64_ii A64_jj) and |Atb - b64| / (sqrt(A64_ii) |r|), |r| = the 2-norm of absres, exactly as _entry_errors of
+    tests/test_gpu_syrk_f16_pipeline.py; a block that does not exist (K = 0) reports 0."""
+    A64, b64 = np.asarray(A64, np.float64), np.asarray(b64, np.float64)
+    dg = np.sqrt(np.maximum(np.diag(A64), 1e-300))
+    eA = np.abs(np.asarray(AtA).astype(np.float64) - A64) / np.outer(dg, dg)
+    rs = float(np.sqrt((np.asarray(absres).astype(np.float64) ** 2).sum()))
+    eb = np.abs(np.asarray(Atb).astype(np.float64).reshape(-1) - b64.reshape(-1)) / (dg * max(rs, 1e-30))
+    o, P = 6 * pairs, A64.shape[0]
+    err, arg = {}, {}
+
+    def put(name, block, r0, c0):
+        if block.size == 0:
+            err[name], arg[name] = 0.0, None
+            return
+        i = np.unravel_index(int(np.argmax(block)), block.shape)
+        err[name] = float(block[i])
+        arg[name] = (r0 + int(i[0]), c0 + int(i[1])) if block.ndim == 2 else (r0 + int(i[0]),)
+    put("pose_pose", eA[:o, :o], 0, 0)
+    put("pose_depth", np.maximum(eA[:o, o:], eA[o:, :o].T), 0, o)
+    put("depth_depth", eA[o:, o:], o, o)
+    put("atb_pose", eb[:o], 0, 0)
+    put("atb_depth", eb[o:P], o, 0)
+    return err, arg
+
+
+def max_norm_errors(AtA, Atb, A64, b64):
+    """the gate of the other modules (tests/test_gpu_parity.py:38): max|got - want| / max|want|, of AtA and of Atb"""
+    rel = lambda g, w: float(np.abs(np.asarray(g, np.float64) - w).max() / max(np.abs(w).max(), 1e-30))     # noqa: E731
+    return rel(AtA, np.asarray(A64, np.float64)), rel(np.asarray(Atb).reshape(-1), np.asarray(b64, np.float64).reshape(-1))
+
+
+def fmt(err):
+    return " ".join("%.2e" % err[k] for k in BLOCKS)
+
+
+# ---- mutations ----------------------------------------------------------------------------------------------------------------
+# wrong-but-plausible results made from the float64 twin: f(case, tw) -> [(A, b)] per window, or None where the mutation does not
+# apply to the case.  Each is an error of the kind a kernel can make in ONE producer while the others stay right.
+EPS = 1e-3
+
+
+def _copy(tw):
+    return [(t.A.copy(), t.b.copy()) for t in tw]
+
+
+def mut_depth_block(case, tw):
+    """the SYRK's depth block off by 1e-3 as a whole"""
+    if case.K == 0:
+        return None
+    o = 6 * case.pairs
+    out = _copy(tw)
+    for A, _ in out:
+        A[o:, o:] *= 1.0 + EPS
+    return out
+
+
+def mut_depth_tile(case, tw):
+    """one 16 x 16 off-diagonal tile of the depth block (block row 0, block column 1, and its mirror image) off by 1e-3"""
+    if case.K < 32:
+        return None
+    o = 6 * case.pairs
+    out = _copy(tw)
+    for A, _ in out:
+        A[o:o + 16, o + 16:o + 32] *= 1.0 + EPS
+        A[o + 16:o + 32, o:o + 16] *= 1.0 + EPS
+    return out
+
+
+def mut_pose_depth_of_one_frame(case, tw):
+    """the pose x depth block of the last target frame off by 1e-3"""
+    if case.K == 0:
+        return None
+    o, f = 6 * case.pairs, 6 * (case.pairs - 1)
+    out = _copy(tw)
+    for A, _ in out:
+        A[f:f + 6, o:] *= 1.0 + EPS
+        A[o:, f:f + 6] *= 1.0 + EPS
+    return out
+
+
+def _records_of_another_mask(case, tw, mask):
+    """what the SYRK gives when some pixels' records are left out: the depth block, the pose x depth blocks and the depth part of Atb
+    of the twin evaluated with `mask`; the pose block and the pose part of Atb -- the gather's own sums -- stay"""
+    if case.layout != "dense" or case.K == 0 or np.array_equal(mask, own_mask(tw)):
+        return None
+    other = twin(case, mask)
+    o = 6 * case.pairs
+    out = _copy(tw)
+    for (A, b), t in zip(out, other):
+        A[o:, :] = t.A[o:, :]
+        A[:, o:] = t.A[:, o:]
+        b[o:] = t.b[o:]
+    return out
+
+
+def mut_ragged_last_step(case, tw):
+    """the last N % 32 pixels (the ragged last 32-pixel SYRK step; where N is a multiple of 32, the last pixel row) of every frame
+    left out of the SYRK's sums"""
+    mask = own_mask(tw).copy()
+    n = case.N % 32 or case.W
+    mask[:, :, case.N - n:] = 0
+    return _records_of_another_mask(case, tw, mask)
+
+
+def mut_one_frame_missing_from_the_last_rows(case, tw):
+    """multi-frame windows: the last target frame's pixels of the last 8 pixel rows left out of the SYRK's sums"""
+    if case.pairs < 2:
+        return None
+    mask = own_mask(tw).copy()
+    mask[:, case.pairs - 1, case.N - 8 * case.W:] = 0
+    return _records_of_another_mask(case, tw, mask)
+
+
+MUTATIONS = collections.OrderedDict([
+    ("depth_block", mut_depth_block), ("depth_tile", mut_depth_tile), ("pose_depth_of_one_frame", mut_pose_depth_of_one_frame),
+    ("ragged_last_step", mut_ragged_last_step), ("one_frame_missing_from_the_last_rows", mut_one_frame_missing_from_the_last_rows)])
+SCALING_MUTATIONS = ("depth_block", "depth_tile", "pose_depth_of_one_frame")
+
+
+def max_norm_asserted(mutation, case):
+    """the pairings on which test_assembly_cases_cpu.py ASSERTS that the max-norm gate (3e-5) passes the mutation: the three scaling
+    mutations on the small-motion scenes, where it is at most 3.3e-6.  Dropped from that assertion, still printed and still held to
+    the entry-wise one:
+      * the large-motion scenes -- with up to 60 % of a frame outside the image the pose block shrinks against the depth block, the
+        max-norm error of the scaling mutations is 1e-6 .. 1.3e-4 there and the old gate sees about a third of the pairings;
+      * the two left-out-pixels mutations -- on shapes of 483 .. 1961 pixels a ragged step or the last 8 rows of one frame are 0.2 .. 35 %
+        of a frame's pixels, and the max-norm gate sees most of them through the pose x depth block (9e-6 .. 8e-2); what it cannot
+        see at the sizes of the product, the entry-wise metric sees here by two to four decades."""
+    return mutation in SCALING_MUTATIONS and case.motion == "small"
+
+
+# ---- the plans, asked of plan.hpp -----------------------------------------------------------------------------------------------
+def plan_rows(cases, cus=MI355X_CUS):
+    """plan_assemble (banet_amd/csrc/plan.hpp compiled with g++, tests/native/plan_host.cpp) for every case at `cus` compute units
+    -> [dict field -> value]"""
+    import atexit
+    import shutil
+    import tempfile
+
+    import test_plan_cpu as tp
+    tmp = tempfile.mkdtemp(prefix="banet_plan_")
+    atexit.register(shutil.rmtree, tmp, True)
+    L = tp.build_host_lib(tmp)
+    names = tp.fields(L)
+    desc = np.asarray([(B_WINDOWS, c.N, c.C, c.K, c.H, c.W, int(c.layout == "dense"), int(c.layout == "sparse"), c.pairs, 0,
+                        c.flags) for c in cases], np.int64).astype(np.int32)
+    out = np.zeros((len(cases), len(names)), np.int64)
+    L.banet_test_plan_sweep(np.ascontiguousarray(desc).ctypes.data_as(ctypes.c_void_p), len(cases), cus, out.ctypes.data_as(ctypes.c_void_p))
+    return [dict(zip(names, row.tolist())) for row in out]
+
+
+def selection_of_plan(row, K):
+    g = 4 if row["g.quad"] else 3 if row["g.strip"] else 2 if row["g.patch"] else 1 if row["g.c128"] else 0
+    s = -1000 if K == 0 else 4 if row["s.f16"] else row["s.direct"]
+    return g, s

@@ -138,6 +138,16 @@ class MarginalsOut(ctypes.Structure):
     _fields_ = [("pose_cov", _FP), ("depth_var", _FP), ("wfactor", _FP), ("logdet", _FP), ("status", _FP)]
 
 
+class MarginalsGradIn(ctypes.Structure):
+    """mirror of banet_marginals_grad_in_t (banet_ba_marginals_grad_f32: the upstream gradients, each optional = zeros)"""
+    _fields_ = [("g_pose_cov", _FP), ("g_depth_var", _FP), ("g_logdet", _FP)]
+
+
+class MarginalsGradOut(ctypes.Structure):
+    """mirror of banet_marginals_grad_out_t (status required, the others optional)"""
+    _fields_ = [("gAtA", _FP), ("gdamping", _FP), ("gsigma2", _FP), ("gbasis", _FP), ("status", _FP)]
+
+
 class ReprojectOut(ctypes.Structure):
     """mirror of banet_reproject_out_t (banet_depth_reproject_f32: both required)"""
     _fields_ = [("depth", _FP), ("index", _FP)]
@@ -178,6 +188,9 @@ EXPORTS = {
                                                   ctypes.c_int, _FP, ctypes.c_size_t, _FP]),
     "banet_ba_marginals_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.c_int]),
     "banet_ba_marginals_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(MarginalsOut), _FP, ctypes.c_size_t, _FP]),
+    "banet_ba_marginals_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.c_int]),
+    "banet_ba_marginals_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(MarginalsGradIn), ctypes.POINTER(MarginalsGradOut),
+                                                   _FP, ctypes.c_size_t, _FP]),
     "banet_depth_reproject_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),
     "banet_depth_reproject_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 3 + [ctypes.POINTER(ReprojectOut), _FP, ctypes.c_size_t, _FP]),
     "banet_basis_fit_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level)]),

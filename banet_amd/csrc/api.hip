@@ -340,6 +340,27 @@ int banet_ba_marginals_f32(const banet_level_t* lv, const float* AtA, const floa
   return launch_marginals(lv, pl, AtA, damping, sigma2, out, ws, static_cast<hipStream_t>(stream));
 }
 
+size_t banet_ba_marginals_grad_workspace_bytes(const banet_level_t* lv, int want_gbasis) {
+  MargGradPlan pl;
+  if (plan_marginals_grad(lv, want_gbasis, &pl) != BANET_OK) return 0;
+  return pl.bytes;
+}
+
+int banet_ba_marginals_grad_f32(const banet_level_t* lv, const float* AtA, const float* damping, const float* sigma2,
+                                const banet_marginals_grad_in_t* in, const banet_marginals_grad_out_t* out, void* ws,
+                                size_t workspace_bytes, banet_stream_t stream) {
+  if (!lv || !AtA || !in || !out || !out->status) return BANET_ERR_INVALID_ARG;
+  if (lv->B < 1 || lv->K < 0 || lv->pairs < 0) return BANET_ERR_INVALID_ARG;
+  const bool want_gb = out->gbasis != nullptr && lv->K > 0;      // gbasis / g_depth_var of a level without a basis: ignored
+  const bool reads_basis = lv->K > 0 && (in->g_depth_var != nullptr || out->gbasis != nullptr);
+  if (reads_basis && (!lv->basis || lv->N < 1)) return BANET_ERR_INVALID_ARG;
+  MargGradPlan pl;
+  const int rc = plan_marginals_grad(lv, want_gb, &pl);
+  if (rc != BANET_OK) return rc;
+  if (!ws || workspace_bytes < pl.bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
+  return launch_marginals_grad(lv, pl, AtA, damping, sigma2, in, out, ws, static_cast<hipStream_t>(stream));
+}
+
 size_t banet_depth_reproject_workspace_bytes(const banet_level_t* lv) {
   size_t bytes = 0;
   if (plan_reproject(lv, &bytes) != BANET_OK) return 0;

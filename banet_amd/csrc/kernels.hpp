@@ -90,6 +90,21 @@ int plan_marginals(const banet_level_t* lv, int want_depth_var, MargPlan* pl);
 int launch_marginals(const banet_level_t* lv, const MargPlan& pl, const float* AtA, const float* damping, const float* sigma2,
                      const banet_marginals_out_t* out, void* ws, hipStream_t s);
 
+// ---- marginals_grad.hip: the backward of the above (banet_ba_marginals_grad_f32) ----
+struct MargGradPlan {   // the workspace of one call; host memory only
+  int P, m, K, NR, NP;  // NR 32-column blocks of the depth block, NP = NR (NR + 1) / 2 lower 32 x 32 blocks of M = sum g b b^T
+  int chunk, rows;      // M's partial rows per window (pixels per row, rows): functions of N alone
+  bool big;             // the factor kernel's packed triangle of Y lives in the workspace: P >= 200, MargPlan's switch by the same
+                        // arithmetic (P (P + 1) / 2 + 2 P doubles against 160 KB of LDS).  Hinv (a second packed triangle) and
+                        // X = Hinv Gbar [P][P] are in the workspace at every P
+  size_t lds;           // the factor kernel's dynamic LDS
+  size_t off_part, off_M, off_T, off_Hinv, off_X, off_big, bytes;
+};
+// reads lv->B / N / K / pairs only (N sizes M's partial rows; < 1 counts as 1); the return codes of plan_marginals
+int plan_marginals_grad(const banet_level_t* lv, int want_gbasis, MargGradPlan* pl);
+int launch_marginals_grad(const banet_level_t* lv, const MargGradPlan& pl, const float* AtA, const float* damping, const float* sigma2,
+                          const banet_marginals_grad_in_t* in, const banet_marginals_grad_out_t* out, void* ws, hipStream_t s);
+
 // ---- reproject.hip: the key frame's depth map in the target frames' pixel grids, z-buffered (banet_depth_reproject_f32) ----
 // reads lv->B / N / K / H / W / dense / scale / pairs only; BANET_ERR_INVALID_ARG (NULL, a non-positive size, N != H W, scale <= 0)
 // or BANET_ERR_UNSUPPORTED (a sparse level); *bytes = the 64-bit keys [B][max(pairs, 1)][H][W]

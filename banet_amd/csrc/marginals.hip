@@ -9,17 +9,9 @@
 //   (b) marg_depthvar_kernel the pass over the basis [B,N,K]: depth_var[n] = sigma^2 |T basis[n,:]|^2 on the f32-input MFMA
 //       (v_mfma_f32_32x32x2_f32: an exact float32 fma chain), y = T b never leaves the accumulators.
 // No atomics; nothing depends on B: a window's bits are the same alone and in any batch.
-#include "kernels.hpp"
+#include "marginals_common.hpp"   // the factorisation and y = T b, shared with marginals_grad.hip
 
 namespace banet {
-
-constexpr int kMargThreads = 1024;       // (a): 16 columns x 64 rows of threads over the trailing blocks
-constexpr int kMargCols = 16, kMargRows = kMargThreads / kMargCols;
-constexpr int kDvThreads = 512;          // (b): 8 waves, 32 pixels each per step
-constexpr int kDvWaves = kDvThreads / 64;
-constexpr size_t kMargLdsMax = 160 * 1024;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 int plan_marginals(const banet_level_t* lv, int want_depth_var, MargPlan* pl) {
   if (!lv || lv->B < 1 || lv->K < 0 || lv->pairs < 0) return BANET_ERR_INVALID_ARG;
@@ -53,8 +45,6 @@ struct MargArgs {
   double* big;   // [B][P (P + 1) / 2] in the workspace when the matrix does not fit the LDS
 };
 
-__device__ __forceinline__ int tri(int i) { return i * (i + 1) / 2; }   // offset of row i of a packed lower triangle
-
 // ---- (a) ------------------------------------------------------------------------------------------------------------------------
 template <bool BIG>
 __global__ __launch_bounds__(kMargThreads) void marg_factor_kernel(const MargArgs a) {
@@ -72,37 +62,7 @@ __global__ __launch_bounds__(kMargThreads) void marg_factor_kernel(const MargArg
   float* wf = a.wfactor ? a.wfactor + (size_t)b * K * K : nullptr;
   float* Tw = a.T ? a.T + (size_t)b * K * K : nullptr;
 
-  for (int i = ty; i < P; i += kMargRows)
-    for (int j = tx; j <= i; j += kMargCols) {
-      double v = (double)A[(size_t)i * P + j];
-      if (i == j) v = v + mu * (v + 1e-5);                // every diagonal entry, the last one included
-      M[tri(i) + j] = v;
-    }
-  __syncthreads();
-
-  // Cholesky, right-looking: column j scaled by 1 / L_jj, then the rank-1 update of the trailing lower triangle
-  bool ok = true;
-  for (int j = 0; j < P; ++j) {
-    const double p = M[tri(j) + j];
-    if (!(p > 0.0) || !(p < __builtin_huge_val())) {      // pivot <= 0 or not finite (a NaN / inf elsewhere reaches a later pivot)
-      ok = false;
-      break;                                              // uniform: every thread read the same pivot
-    }
-    const double d = sqrt(p);
-    for (int i = j + 1 + tid; i < P; i += kMargThreads) {
-      const double v = M[tri(i) + j] / d;
-      M[tri(i) + j] = v;
-      colbuf[i] = v;
-    }
-    if (tid == 0) diag[j] = d;
-    __syncthreads();
-    for (int i = j + 1 + ty; i < P; i += kMargRows) {
-      const double li = colbuf[i];
-      double* row = M + tri(i);
-      for (int k = j + 1 + tx; k <= i; k += kMargCols) row[k] = fma(-li, colbuf[k], row[k]);
-    }
-    __syncthreads();
-  }
+  const bool ok = marg_cholesky(A, mu, P, M, colbuf, diag);   // H into M, then L in place; uniform
 
   if (!ok) {
     for (int idx = tid; idx < m * m; idx += kMargThreads) cov[idx] = (idx / m == idx % m) ? __builtin_huge_valf() : 0.f;
@@ -124,22 +84,7 @@ __global__ __launch_bounds__(kMargThreads) void marg_factor_kernel(const MargArg
     if (tid == 0) a.logdet[b] = (float)(2.0 * s);
   }
 
-  // Y = L^-1 in place: column sweep of L Y = I.  Before step k, row i >= k holds the running right-hand side
-  // R[i,c] = delta_ic - sum_{j<k} L[i,j] Y[j,c] in its columns c < k (1 on the diagonal, implied) and L in its columns >= k.
-  for (int k = 0; k < P; ++k) {
-    const double d = diag[k];
-    double* rk = M + tri(k);
-    for (int c = tid; c < k; c += kMargThreads) rk[c] = rk[c] / d;
-    for (int i = k + 1 + tid; i < P; i += kMargThreads) colbuf[i] = M[tri(i) + k];
-    if (tid == 0) rk[k] = 1.0 / d;
-    __syncthreads();
-    for (int i = k + 1 + ty; i < P; i += kMargRows) {
-      const double li = colbuf[i];
-      double* row = M + tri(i);
-      for (int c = tx; c <= k; c += kMargCols) row[c] = fma(-li, rk[c], c == k ? 0.0 : row[c]);
-    }
-    __syncthreads();
-  }
+  marg_invert_lower(P, M, colbuf, diag);   // Y = L^-1 in place
 
   // T = the trailing K x K block of Y, strict upper triangle as zeros; rounded to float32 once
   if (wf || Tw)
@@ -162,19 +107,14 @@ __global__ __launch_bounds__(kMargThreads) void marg_factor_kernel(const MargArg
 }
 
 // ---- (b) ------------------------------------------------------------------------------------------------------------------------
-// T lives in LDS as its NR (NR + 1) / 2 lower 32 x 32 blocks (rows / columns >= K as zeros; the all-zero upper blocks do not exist):
-// block (R, Cb) at R (R + 1) / 2 + Cb, rows of 32 floats whose eight 16-byte chunks are XOR-swizzled by the row (ds_read_b128 of
-// one chunk column by 32 rows: no bank conflicts, no padding -- K = 256 is 36 blocks = 144 KB).
-// A wave computes Y^T = T B^T for 32 pixels: A operand = T (lane l: row l & 31 of the block), B operand = the pixel's basis row
-// (lane l: pixel l & 31), k slot l >> 5.  Both operands use the same column order inside a 32-column block, chunk 2 q + (l >> 5),
-// element e: column 8 q + 4 (l >> 5) + e at MFMA step 4 q + e, so a lane's four steps are one 16-byte load on either side.
-// The result has the pixel on the lane and the rows of T in the registers: sum of squares per lane, one cross-half add.
+// T lives in LDS as its lower 32 x 32 blocks (marg_fill_T_image) and a wave computes y = T b for 32 pixels (marg_tile_y; the
+// layouts: marginals_common.hpp).  The result has the pixel on the lane and the rows of T in the registers: sum of squares per
+// lane, one cross-half add.
 template <int NR>
 __global__ __launch_bounds__(kDvThreads) void marg_depthvar_kernel(const float* __restrict__ basis, const float* __restrict__ Tws,
                                                                    const float* __restrict__ sigma2, const int32_t* __restrict__ status,
                                                                    float* __restrict__ depth_var, int N, int K, int tiles, int vec4) {
   extern __shared__ __attribute__((aligned(16))) float sT[];
-  constexpr int NB = NR * (NR + 1) / 2;
   const int b = blockIdx.y, tid = threadIdx.x;
   float* out = depth_var + (size_t)b * N;
   if (status[b] != 0) {                                   // uniform per workgroup
@@ -182,15 +122,7 @@ __global__ __launch_bounds__(kDvThreads) void marg_depthvar_kernel(const float* 
     return;
   }
   const float* T = Tws + (size_t)b * K * K;
-  for (int idx = tid; idx < NB * 1024; idx += kDvThreads) {
-    const int blk = idx >> 10, i = (idx >> 5) & 31, j = idx & 31;
-    int R = 0;
-    while ((R + 1) * (R + 2) / 2 <= blk) ++R;
-    const int Cb = blk - R * (R + 1) / 2;
-    const int r = 32 * R + i, c = 32 * Cb + j;
-    const float v = (r < K && c <= r) ? T[r * K + c] : 0.f;
-    sT[blk * 1024 + i * 32 + ((((j >> 2) ^ (i & 7))) << 2) + (j & 3)] = v;
-  }
+  marg_fill_T_image<NR>(sT, T, K);
   __syncthreads();
 
   const int lane = tid & 63, wave = tid >> 6, nl = lane & 31, h = lane >> 5;
@@ -201,48 +133,8 @@ __global__ __launch_bounds__(kDvThreads) void marg_depthvar_kernel(const float* 
     const int n = tile * 32 + nl;
     const bool valid = n < N;
     const float* row = Bw + (size_t)(valid ? n : 0) * K;
-    int trow = nl * 32;                                   // opaque per tile: the reads of T stay inside the loop (hoisted out of
-    asm volatile("" : "+v"(trow));                        // it, the blocks of T would occupy up to 576 registers)
-    // a lane's 16 floats of column block Cb: columns 32 Cb + 8 q + 4 h + e; zeros past the row's end and for pixels past N
-    auto load_block = [&](int Cb, f32x4* dst) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c0 = 32 * Cb + 8 * q + 4 * h;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (vec4) {
-          if (valid && c0 < K) v = *reinterpret_cast<const f32x4*>(row + c0);   // K % 4 == 0: the chunk is inside the row
-        } else if (valid) {
-          if (c0 + 0 < K) v[0] = row[c0 + 0];
-          if (c0 + 1 < K) v[1] = row[c0 + 1];
-          if (c0 + 2 < K) v[2] = row[c0 + 2];
-          if (c0 + 3 < K) v[3] = row[c0 + 3];
-        }
-        dst[q] = v;
-      }
-    };
     f32x16 acc[NR];
-#pragma unroll
-    for (int R = 0; R < NR; ++R)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[R][i] = 0.f;
-    f32x4 cur[4], nxt[4];
-    load_block(0, cur);
-#pragma unroll
-    for (int Cb = 0; Cb < NR; ++Cb) {
-      if (Cb + 1 < NR) load_block(Cb + 1, nxt);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int R = Cb; R < NR; ++R) {                   // the blocks above the diagonal are zero: skipped
-          const int blk = R * (R + 1) / 2 + Cb;
-          const f32x4 t = *reinterpret_cast<const f32x4*>(&sT[blk * 1024 + trow + (((2 * q + h) ^ (nl & 7)) << 2)]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[R] = __builtin_amdgcn_mfma_f32_32x32x2f32(t[e], cur[q][e], acc[R], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-    }
+    marg_tile_y<NR>(sT, row, valid, K, vec4, nl, h, acc);
     float ss = 0.f;
 #pragma unroll
     for (int R = 0; R < NR; ++R)

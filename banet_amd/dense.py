@@ -215,14 +215,21 @@ class DenseBA:
                             r.proj.reshape(shape + (2,)) if proj else None, r.sums)
 
     def marginals(self, level_index, state=None, R=None, T=None, Wc=None, damping=0.0, sigma2="residual",
-                  want=("pose_cov", "depth_var")):
+                  want=("pose_cov", "depth_var"), differentiable=False):
         """How sure is the solve?  The posterior marginals of level `level_index` at a state (an LmState, or R / T / Wc; default:
         new_state()): one assembly pass (ops.ba_assemble, the exact SYRK form) for the normal matrix, then ops.ba_marginals ->
         DenseMarginals(pose_cov [B,6 pairs,6 pairs], depth_var [B,H,W], wfactor, logdet, status [B], sigma2 [B] or None, damping [B]
         or None -- the last two as they were passed on).
         sigma2: "residual" = the residual variance at the state, sum_f sum sq / max(C sum_f count - P, 1) from residual().sums;
         None = 1; a float or a tensor [B] is passed through.  damping: a float, a tensor [B], or "lambda" = state.lambda_out (the
-        last lambda of the solve).  No host sync."""
+        last lambda of the solve).  No host sync.
+        differentiable=True: the outputs are attached to the autograd graph -- dense_train.assemble_differentiable, then
+        ops.ba_marginals_diff; sigma2="residual" from the maps of ops.ba_residual_diff with torch sums.  Gradients of pose_cov,
+        depth_var and logdet reach R / T / Wc as given (or the state's tensors) and the level's src / tgt / depth / basis, and
+        damping / sigma2 where they are tensors that require grad; wfactor and status carry none.  The levels the dense adjoint
+        takes (bundle, bundle_camera)."""
+        if differentiable:
+            return self._marginals_differentiable(level_index, state, R, T, Wc, damping, sigma2, want)
         p = self.problems[level_index]
         if isinstance(damping, str):
             if damping != "lambda":
@@ -239,6 +246,32 @@ class DenseBA:
             sigma2 = sums[:, :, 0].sum(dim=1) / torch.clamp(p.C * sums[:, :, 2].sum(dim=1) - float(p.P), min=1.0)
         AtA = ops.ba_assemble(p, st.R, st.T, wc)[0]
         m = ops.ba_marginals(p, AtA, damping=damping, sigma2=sigma2, want=want)
+        dv = m.depth_var.reshape(p.B, int(p.c.H), int(p.c.W)) if m.depth_var is not None else None
+        as_t = lambda v: v if (v is None or torch.is_tensor(v)) else torch.full((p.B,), float(v), dtype=torch.float32, device=p.device)
+        return DenseMarginals(m.pose_cov, dv, m.wfactor, m.logdet, m.status, as_t(sigma2), as_t(damping))
+
+    def _marginals_differentiable(self, level_index, state, R, T, Wc, damping, sigma2, want):
+        from . import dense_train
+        p = self.problems[level_index]
+        if isinstance(damping, str):
+            if damping != "lambda":
+                raise ops.capi.BanetError("DenseBA.marginals: damping is a number, a tensor or \"lambda\"")
+            if state is None:
+                raise ops.capi.BanetError("DenseBA.marginals: damping=\"lambda\" needs the solved state")
+            damping = state.lambda_out
+        if state is not None:
+            R, T, Wc = state.R, state.T, state.Wc
+        elif R is None or T is None or (self.K > 0 and Wc is None):
+            st = self.new_state(R, T, Wc)
+            R, T, Wc = (st.R if R is None else R), (st.T if T is None else T), (st.Wc if Wc is None else Wc)
+        wc = Wc if self.K > 0 else None
+        if isinstance(sigma2, str):
+            if sigma2 != "residual":
+                raise ops.capi.BanetError("DenseBA.marginals: sigma2 is None, a number, a tensor or \"residual\"")
+            sq, _, mask, _ = ops.ba_residual_diff(p, R, T, wc)
+            sigma2 = sq.sum(dim=(1, 2)) / torch.clamp(p.C * mask.sum(dim=(1, 2)).to(sq.dtype) - float(p.P), min=1.0)
+        AtA = dense_train.assemble_differentiable(self, level_index, R, T, wc)[0]
+        m = ops.ba_marginals_diff(p, AtA, damping=damping, sigma2=sigma2, want=want)
         dv = m.depth_var.reshape(p.B, int(p.c.H), int(p.c.W)) if m.depth_var is not None else None
         as_t = lambda v: v if (v is None or torch.is_tensor(v)) else torch.full((p.B,), float(v), dtype=torch.float32, device=p.device)
         return DenseMarginals(m.pose_cov, dv, m.wfactor, m.logdet, m.status, as_t(sigma2), as_t(damping))

@@ -460,6 +460,103 @@ class _LevelSolve(torch.autograd.Function):
                 None if s_bas is None else dbasis.reshape(s_bas), gR.reshape(s_R), gT.reshape(s_T), gW) + tuple(glayers)
 
 
+class _AssembleDiff(torch.autograd.Function):
+    """ops.ba_assemble of one dense level as an autograd node -> (AtA, Atb, absres, nvalid).  The backward is dense_adjoint with
+    the incoming gAtA / gAtb / gabs (zeros where absent), per target frame on E_i^T gAtA E_i exactly as _LevelSolve.backward."""
+
+    @staticmethod
+    def forward(ctx, ba, li, src, tgt, depth, basis, R, T, Wc):
+        prob = ba.problems[li]
+        AtA, Atb, absres, nvalid = ops.ba_assemble(prob, R, T, Wc if prob.K > 0 else None)
+        ctx.ba, ctx.li = ba, li
+        ctx.save_for_backward(R, T, Wc)
+        ctx.shapes = (src.shape, tgt.shape, depth.shape, None if basis is None else basis.shape, R.shape, T.shape, Wc.shape)
+        ctx.mark_non_differentiable(nvalid)
+        ctx.set_materialize_grads(False)
+        return AtA, Atb, absres, nvalid
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gAtA, gAtb, gabs, _gn):
+        if gAtA is None and gAtb is None and gabs is None:
+            return (None,) * 9
+        ba, li = ctx.ba, ctx.li
+        prob = ba.problems[li]
+        R, T, Wc = ctx.saved_tensors
+        pairs, dev = prob.pairs, prob.device
+        B, N, C, K, H, W = prob.B, prob.N, prob.C, prob.K, prob.c.H, prob.c.W
+        P = 6 * pairs + K
+        gAtA = torch.zeros(B, P, P, device=dev) if gAtA is None else gAtA.contiguous()
+        gAtb = torch.zeros(B, P, device=dev) if gAtb is None else gAtb.reshape(B, P).contiguous()
+        gabs = torch.zeros(B, C, device=dev) if gabs is None else gabs.contiguous()
+        pprobs = [prob] if pairs == 1 else _pair_problems(ba, li)
+        fold = FOLD_MODE != "0" and capi.lib().banet_dense_adjoint_workspace_bytes_ex(ctypes.byref(pprobs[0].c), ADJOINT_FOLD_TARGET) != 0
+        dsrc = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+        dmap3 = [torch.empty((B, H, W, C if fold else 3 * C), dtype=torch.float32, device=dev) for _ in range(pairs)]
+        ddepth = torch.empty((B, N), dtype=torch.float32, device=dev)
+        dbasis = torch.empty((B, N, K), dtype=torch.float32, device=dev)
+        Rv, Tv = R.reshape(B, pairs, 3, 3), T.reshape(B, pairs, 3, 1)
+        gR, gT = torch.empty(B, pairs, 3, 3, device=dev), torch.empty(B, pairs, 3, 1, device=dev)
+        gW = torch.zeros(B, K, 1, device=dev)
+        o, ws = 6 * pairs, None
+        for i in range(pairs):
+            if pairs == 1:
+                gA_i, gb_i = gAtA, gAtb
+            else:       # E_i^T (dL/dAtA) E_i: the frame's pose block, its cross blocks with the depth block, the depth block
+                idx = torch.cat([torch.arange(6 * i, 6 * i + 6, device=dev), torch.arange(o, o + K, device=dev)])
+                gA_i = gAtA.index_select(1, idx).index_select(2, idx).contiguous()
+                gb_i = gAtb.index_select(1, idx).contiguous()
+            dpose, ws = dense_adjoint(pprobs[i], Rv[:, i].contiguous(), Tv[:, i].contiguous(), Wc, gA_i, gb_i, gabs, dsrc, dmap3[i], ddepth,
+                                      dbasis, ws, overwrite=i == 0, overwrite_map=True, fold=fold,
+                                      extra_flags=ADJOINT_REUSE_DEPTH_SEED if (i > 0 and REUSE_MODE != "0") else 0)
+            gR[:, i] = dpose[:, 0:9].reshape(B, 3, 3)
+            gT[:, i] = dpose[:, 9:12].reshape(B, 3, 1)
+            gW += dpose[:, 12:].reshape(B, K, 1)
+        if fold:                                           # dmap3[i] IS the frame's target gradient
+            dtgt = dmap3[0] if pairs == 1 else torch.stack(dmap3, 1)
+        else:
+            dtgt = torch.empty((B, pairs, H, W, C), dtype=torch.float32, device=dev)
+            for i in range(pairs):
+                di = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+                target_map_adjoint(dmap3[i], di, overwrite=True)
+                dtgt[:, i] = di
+        s_src, s_tgt, s_dep, s_bas, s_R, s_T, s_W = ctx.shapes
+        return (None, None, dsrc.reshape(s_src), dtgt.reshape(s_tgt), ddepth.reshape(s_dep), None if s_bas is None else dbasis.reshape(s_bas),
+                gR.reshape(s_R), gT.reshape(s_T), gW.reshape(s_W))
+
+
+def assemble_differentiable(ba, level_index, R, T, Wc=None):
+    """ops.ba_assemble on level `level_index` of a DenseBA at (R, T, Wc), attached to the autograd graph -> (AtA [B,P,P], Atb [B,P],
+    absres [B,C], nvalid [B]): AtA, Atb and absres are differentiable with respect to R, T, Wc and the level's src / tgt / depth /
+    basis (ba.levels[level_index]) through banet_dense_adjoint_ex_f32, one call per target frame.  The levels the dense adjoint
+    takes: `bundle` (1 <= K <= 256) and `bundle_camera`, dense layout, C <= 256; BanetError otherwise."""
+    prob, lv = ba.problems[level_index], ba.levels[level_index]
+    one = capi.Level.from_buffer_copy(bytes(prob.c))       # the two-frame view the adjoint kernels take
+    one.pairs = 1
+    if ba.variant not in ("bundle", "bundle_camera") or not int(prob.c.dense) or \
+            capi.lib().banet_dense_adjoint_workspace_bytes_ex(ctypes.byref(one), 0) == 0:
+        raise capi.BanetError("assemble_differentiable: a dense bundle (1 <= K <= 256) or bundle_camera level with C <= 256 is needed")
+    dev = prob.device
+    Wc = torch.zeros(prob.B, prob.K, 1, device=dev) if (Wc is None or prob.K == 0) else Wc
+    return _AssembleDiff.apply(ba, level_index, lv.src, lv.tgt, lv.depth, lv.basis if prob.K > 0 else None, capi.f32c(R), capi.f32c(T),
+                               capi.f32c(Wc))
+
+
+def depth_nll_loss(depth, depth_var, depth_gt, mask=None, var_floor=1e-12):
+    """The Gaussian negative log-likelihood of a depth map under its posterior variance (DenseBA.marginals(differentiable=True)
+    .depth_var), 0.5 (log var + (depth - depth_gt)^2 / var) with var = max(depth_var, var_floor), as the mean over the pixels of
+    `mask` (None: all) per window -> [B].  A window whose variance is not finite anywhere (status 1: depth_var = +inf) is left out:
+    its loss is 0 and it sends no gradient -- zeros, not NaN."""
+    B = depth_var.shape[0]
+    var, d, gt = depth_var.reshape(B, -1), depth.reshape(B, -1), depth_gt.reshape(B, -1)
+    keep = torch.isfinite(var)
+    if mask is not None:
+        keep = keep & mask.reshape(B, -1).bool()
+    var = torch.where(keep, var, torch.ones_like(var)).clamp(min=float(var_floor))   # (the pixels left out: a harmless 1, no inf - inf)
+    nll = 0.5 * (torch.log(var) + (d - gt) ** 2 / var)
+    return torch.where(keep, nll, torch.zeros_like(nll)).sum(1) / keep.sum(1).clamp(min=1)
+
+
 def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=None, Wc=None, outputs=None):
     """Differentiable DenseBA.solve with fixed iteration counts: `levels` = the DenseLevel objects `ba` was built from (their
     src / tgt / depth / basis tensors may require grad), `lambda_weights` = per level five (filters, biases) pairs (tensors

@@ -346,6 +346,19 @@ MARGINALS_OUTPUTS = ("pose_cov", "depth_var", "wfactor", "logdet")
 Marginals = collections.namedtuple("Marginals", "pose_cov depth_var wfactor logdet status")
 
 
+def _per_window(v, name, B, dev, who):
+    """damping / sigma2 of the marginals entries: None, a float or a tensor of 1 or B values -> None or a float32 tensor [B]"""
+    if v is None:
+        return None
+    t = v if torch.is_tensor(v) else torch.full((B,), float(v), dtype=torch.float32, device=dev)
+    t = capi.f32c(t).reshape(-1)
+    if t.numel() == 1 and B > 1:
+        t = t.expand(B).contiguous()
+    if t.numel() != B:
+        raise capi.BanetError("%s: %s must be a float or hold B = %d values" % (who, name, B))
+    return t
+
+
 def ba_marginals_workspace_bytes(problem, want_depth_var=True):
     """banet_ba_marginals_workspace_bytes (0 = unsupported: K > 256 or P > 304)"""
     return int(capi.lib().banet_ba_marginals_workspace_bytes(ctypes.byref(problem.c), int(bool(want_depth_var))))
@@ -374,18 +387,7 @@ def ba_marginals(problem, AtA, damping=None, sigma2=None, want=("pose_cov", "dep
     if unknown:
         raise capi.BanetError("ba_marginals: unknown outputs %s" % unknown)
 
-    def per_window(v, name):
-        if v is None:
-            return None
-        t = v if torch.is_tensor(v) else torch.full((B,), float(v), dtype=torch.float32, device=dev)
-        t = capi.f32c(t).reshape(-1)
-        if t.numel() == 1 and B > 1:
-            t = t.expand(B).contiguous()
-        if t.numel() != B:
-            raise capi.BanetError("ba_marginals: %s must be a float or hold B = %d values" % (name, B))
-        return t
-
-    damping, sigma2 = per_window(damping, "damping"), per_window(sigma2, "sigma2")
+    damping, sigma2 = _per_window(damping, "damping", B, dev, "ba_marginals"), _per_window(sigma2, "sigma2", B, dev, "ba_marginals")
     pD, pS = capi.ptr(damping), capi.ptr(sigma2)
     res = dict(pose_cov=torch.empty((B, m, m), dtype=torch.float32, device=dev),
                depth_var=torch.empty((B, N), dtype=torch.float32, device=dev) if "depth_var" in want and K > 0 else None,
@@ -403,6 +405,105 @@ def ba_marginals(problem, AtA, damping=None, sigma2=None, want=("pose_cov", "dep
     capi.check(L.banet_ba_marginals_f32(ctypes.byref(lv), pA, pD, pS, ctypes.byref(c), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
                                         capi.stream()))
     return Marginals(**res)
+
+
+MARGINALS_GRAD_OUTPUTS = ("gAtA", "gdamping", "gsigma2", "gbasis")
+MarginalsGrad = collections.namedtuple("MarginalsGrad", "gAtA gdamping gsigma2 gbasis status")
+
+
+def ba_marginals_grad(problem, AtA, damping=None, sigma2=None, g_pose_cov=None, g_depth_var=None, g_logdet=None,
+                      want=("gAtA", "gbasis"), ws=None):
+    """banet_ba_marginals_grad_f32: the backward of ba_marginals.  g_pose_cov [B,6 pairs,6 pairs] (need not be symmetric),
+    g_depth_var [B,N], g_logdet [B]: dL/dpose_cov, dL/ddepth_var, dL/dlogdet (None = zeros) ->
+    MarginalsGrad(gAtA [B,P,P] = the gradient with respect to a symmetric AtA, exactly symmetric (the upstream gAtA of
+    dense_train.dense_adjoint), gdamping [B], gsigma2 [B], gbasis [B,N,K], status [B] int32 as ba_marginals); the outputs not named
+    in `want` (and gbasis of a level without a basis) are None.  The factorisation is recomputed from AtA / damping / sigma2
+    (None, a float or a tensor [B], as ba_marginals); a window with status 1 gets zeros.  Every element is written.  Device tensors,
+    no host sync; a window's bits do not depend on the batch nor on `want`."""
+    L = capi.lib()
+    lv = problem.c
+    B, N, K, pairs = int(lv.B), int(lv.N), int(lv.K), max(int(lv.pairs), 1)
+    m, P = 6 * pairs, 6 * pairs + K
+    AtA = capi.f32c(AtA)
+    pA = capi.ptr(AtA)                      # (a CPU tensor: BanetError, before anything is allocated)
+    dev = AtA.device
+    if AtA.numel() != B * P * P:
+        raise capi.BanetError("ba_marginals_grad: AtA must be [B,P,P] = [%d,%d,%d]" % (B, P, P))
+    unknown = [w for w in want if w not in MARGINALS_GRAD_OUTPUTS]
+    if unknown:
+        raise capi.BanetError("ba_marginals_grad: unknown outputs %s" % unknown)
+    damping = _per_window(damping, "damping", B, dev, "ba_marginals_grad")
+    sigma2 = _per_window(sigma2, "sigma2", B, dev, "ba_marginals_grad")
+    gin, keep = capi.MarginalsGradIn(), []
+    for name, g, n in (("g_pose_cov", g_pose_cov, B * m * m), ("g_depth_var", g_depth_var, B * N), ("g_logdet", g_logdet, B)):
+        if g is not None and not (name == "g_depth_var" and K == 0):
+            g = capi.f32c(g)
+            if g.numel() != n:
+                raise capi.BanetError("ba_marginals_grad: %s must hold %d floats" % (name, n))
+            keep.append(g)
+            setattr(gin, name, capi.ptr(g).value)
+    shapes = dict(gAtA=(B, P, P), gdamping=(B,), gsigma2=(B,), gbasis=(B, N, K))
+    res = {name: torch.empty(shapes[name], dtype=torch.float32, device=dev) if name in want and not (name == "gbasis" and K == 0) else None
+           for name in MARGINALS_GRAD_OUTPUTS}
+    res["status"] = torch.empty((B,), dtype=torch.int32, device=dev)
+    c = capi.MarginalsGradOut()
+    for name, t in res.items():
+        setattr(c, name, None if t is None else t.data_ptr())
+    nb = int(L.banet_ba_marginals_grad_workspace_bytes(ctypes.byref(lv), int(res["gbasis"] is not None)))
+    if nb == 0:
+        raise capi.BanetError("ba_marginals_grad: unsupported shape (K <= 256 and P <= 304)")
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, dev)
+    capi.check(L.banet_ba_marginals_grad_f32(ctypes.byref(lv), pA, capi.ptr(damping), capi.ptr(sigma2), ctypes.byref(gin), ctypes.byref(c),
+                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), capi.stream()))
+    del keep
+    return MarginalsGrad(**res)
+
+
+class _MarginalsDiff(torch.autograd.Function):
+    """ba_marginals with banet_ba_marginals_grad_f32 as its backward; the basis enters as an input so that autograd sees it"""
+
+    @staticmethod
+    def forward(ctx, problem, want, AtA, damping, sigma2, basis):
+        m = ba_marginals(problem, AtA, damping=damping, sigma2=sigma2, want=want)
+        ctx.problem = problem
+        ctx.scalars = (None if torch.is_tensor(damping) else damping, None if torch.is_tensor(sigma2) else sigma2)
+        ctx.has = (torch.is_tensor(damping), torch.is_tensor(sigma2))
+        ctx.shapes = [t.shape if torch.is_tensor(t) else None for t in (AtA, damping, sigma2, basis)]
+        ctx.save_for_backward(AtA, *[t for t in (damping, sigma2) if torch.is_tensor(t)])
+        ctx.mark_non_differentiable(*[t for t in (m.wfactor, m.status) if t is not None])
+        ctx.set_materialize_grads(False)      # an output the loss does not use arrives as None = a NULL upstream gradient
+        return m.pose_cov, m.depth_var, m.wfactor, m.logdet, m.status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cov, g_dv, _g_wf, g_ld, _g_status):
+        saved = list(ctx.saved_tensors)
+        AtA = saved.pop(0)
+        damping = saved.pop(0) if ctx.has[0] else ctx.scalars[0]
+        sigma2 = saved.pop(0) if ctx.has[1] else ctx.scalars[1]
+        need = ctx.needs_input_grad[2:]
+        want = tuple(n for n, k in zip(MARGINALS_GRAD_OUTPUTS, need) if k and not (n == "gbasis" and int(ctx.problem.c.K) == 0))
+        if not want or (g_cov is None and g_dv is None and g_ld is None):
+            return (None,) * 6
+        g = ba_marginals_grad(ctx.problem, AtA, damping, sigma2, g_cov, g_dv, g_ld, want=want)
+        out = []
+        for n, shape in zip(MARGINALS_GRAD_OUTPUTS, ctx.shapes):
+            t = getattr(g, n) if n in want else None
+            if t is not None and t.numel() != shape.numel():       # one damping / sigma2 value shared by the windows
+                t = t.sum()
+            out.append(None if t is None else t.reshape(shape))
+        return (None, None) + tuple(out)
+
+
+def ba_marginals_diff(problem, AtA, damping=None, sigma2=None, want=("pose_cov", "depth_var")):
+    """ba_marginals attached to the autograd graph -> Marginals: pose_cov, depth_var and logdet are differentiable with respect to
+    AtA (as a symmetric matrix), the basis the problem was built from, and damping / sigma2 where they are tensors that require
+    grad; wfactor and status are not.  The backward is one banet_ba_marginals_grad_f32 call that asks only for the gradients some
+    input needs; a window with status 1 (depth_var = +inf) sends zeros."""
+    basis = problem.keep[3] if hasattr(problem, "keep") else getattr(problem, "basis", None)
+    res = _MarginalsDiff.apply(problem, tuple(want), AtA, damping, sigma2, basis)
+    return Marginals(*res)
 
 
 Reprojection = collections.namedtuple("Reprojection", "depth index")

@@ -332,6 +332,47 @@ size_t banet_ba_marginals_workspace_bytes(const banet_level_t* lv, int want_dept
 int banet_ba_marginals_f32(const banet_level_t* lv, const float* AtA, const float* damping, const float* sigma2,
                            const banet_marginals_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream);
 
+/* (3d') the backward of (3d): pose_cov, depth_var and logdet as differentiable losses.  From the upstream gradients g_pose_cov
+ *     [B,m,m] (m = 6 max(pairs, 1); need not be symmetric), g_depth_var [B,N] (either sign) and g_logdet [B] -- each or NULL = zeros
+ *     -- with A = AtA[b] as a symmetric matrix, H, L, T, mu, s2 as in (3d), Hinv = H^-1:
+ *         M    = sum_n g_depth_var[n] b_n b_n^T               Gbar = blockdiag(1/2 (g_pose_cov + g_pose_cov^T), M)
+ *         dH   = g_logdet Hinv - s2 Hinv Gbar Hinv             (symmetric)
+ *       gAtA[b]     = dH off the diagonal, (1 + mu) dH on it: the gradient with respect to a SYMMETRIC AtA (through 1/2 (A + A^T)),
+ *                     written in full and exactly symmetric -- the form banet_dense_adjoint_ex_f32 takes as its upstream gAtA
+ *       gdamping[b] = sum_i dH_ii (A_ii + 1e-5)               gsigma2[b] = trace(Hinv Gbar)
+ *       gbasis[b,n] = 2 s2 g_depth_var[n] T^T (T b_n)
+ *       status[b]   = as (3d), by the same test; a window with status 1 gets zeros in every output, and its upstream values are
+ *                     not used; the other windows of the batch are unaffected.
+ *     wfactor has no gradient.  The entry recomputes the factorisation from AtA, damping and sigma2 (float64 on the float32 inputs,
+ *     outputs rounded once): it takes no saved state from (3d).  Every requested output is written in every element: no
+ *     accumulation, no need to pre-zero.  A NULL upstream gives the same bits as a zero-filled one.  Launches: M on the f32-input
+ *     matrix instructions and its fold (with g_depth_var and K > 0), the factor kernel (one workgroup per window), one pass over
+ *     the basis (with gbasis and K > 0: one read of the basis, one write of [N,K]).
+ *     The entry reads lv->B, N, K, pairs and basis and NOTHING else of the level; N and basis only when g_depth_var or gbasis is
+ *     given and K > 0 (gbasis of a level without a basis: ignored).  BANET_ERR_INVALID_ARG, decided before any launch: NULL lv /
+ *     AtA / in / out / out->status; B < 1 (or a negative K / pairs); basis == NULL or N < 1 where they are read.  K > 256 or
+ *     P > 304: workspace_bytes = 0 and BANET_ERR_UNSUPPORTED.  Workspace: required, pure scratch (the contract at the top of this
+ *     file; the query is never 0 for a supported shape), size by the query with the lv of the call (want_gbasis = whether
+ *     out->gbasis will be given); NULL, misaligned or too small: BANET_ERR_WORKSPACE.  Enqueue only, one stream.  No float atomics;
+ *     every summation order depends on N, K and pairs, never on B: a window's bits are the same alone and in any batch; a subset
+ *     of the outputs gives the same bits for that subset.  BANET_VERSION is unchanged: detect the entry by its symbol.          */
+typedef struct banet_marginals_grad_in {
+  const float* g_pose_cov;   /* [B][6 pairs][6 pairs]  or NULL = zeros */
+  const float* g_depth_var;  /* [B][N]                 or NULL = zeros; ignored when K == 0 */
+  const float* g_logdet;     /* [B]                    or NULL = zeros */
+} banet_marginals_grad_in_t;
+typedef struct banet_marginals_grad_out {
+  float* gAtA;       /* [B][P][P]   or NULL */
+  float* gdamping;   /* [B]         or NULL */
+  float* gsigma2;    /* [B]         or NULL */
+  float* gbasis;     /* [B][N][K]   or NULL; ignored when K == 0 */
+  int32_t* status;   /* [B]         required: 0 = ok, 1 = H not positive definite */
+} banet_marginals_grad_out_t;
+size_t banet_ba_marginals_grad_workspace_bytes(const banet_level_t* lv, int want_gbasis);
+int banet_ba_marginals_grad_f32(const banet_level_t* lv, const float* AtA, const float* damping, const float* sigma2,
+                                const banet_marginals_grad_in_t* in, const banet_marginals_grad_out_t* out,
+                                void* ws, size_t workspace_bytes, banet_stream_t stream);
+
 /* (3e) depth transfer to a new key frame: what a window learned about the scene, carried into another frame.  Two entries.
  *   banet_depth_reproject_f32: the key frame's depth map D = depth + basis . Wc (Wc == NULL or K == 0: D = depth) reprojected
  *     into the pixel grid of every target frame f (F = max(pairs, 1); R [B,F,9], T [B,F,3]) with a z-buffer.  Per source pixel n

@@ -86,8 +86,6 @@ static int check_state(const banet_level_t* lv, const banet_mlp_t* mlp, const ba
 }
 
 
-constexpr int kRoleSmallLevel = 19200;   // pixels: levels whose SYRK launch is latency-bound (see the role condition below)
-
 int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, int early_termination,
                   const banet_lm_params_t* params, const banet_state_t* st, void* ws, size_t ws_bytes, LevelRun* run) {
   int rc = check_level(lv);
@@ -116,29 +114,17 @@ int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base
   run->mlp = mlp;
   run->max_iters = max_iters;
   run->lm = early_termination && lv->variant == BANET_LEGACY_LM;
-  run->role = false;
+  run->role = SyrkRole{0, pl.s.Gs};
   if (run->lm) {
     a.ctl = w.ctl;
   } else {
     // the tile queue is reset once per level; afterwards every solve kernel leaves it zeroed for the next gather
     a.queue = assemble_queue(pl, w.partials);
     a.nqueue = 8 * npairs(lv);
-    // bundle levels whose SYRK is ba_syrk_bf16x6_kernel: the lambda MLP runs as a role workgroup of the SYRK launch, off the
-    // solve kernel's critical path (C <= 256: the role's LDS scratch)
-    // ... and coarse levels at any batch (N <= kRoleSmallLevel pixels: their SYRK is a latency chain of 1-3 steps per wave, so a
-    // window's 7 workgroups take what 8 take, and the solve kernel loses the 19 us MLP: 40x30 .. 160x120 x 32 windows).
-    // Small batches only (B <= 8) otherwise: the SYRK kernel runs one workgroup per CU (512 registers per wave), so the role workgroups
-    // need CUs of their own -- at B = 32 (8 + 1 workgroups per window = 288 > 256 CUs) a second round of workgroups doubled
-    // the SYRK time (640x480 x 32: 1326 -> 2457 us); with B <= 8 one SYRK workgroup per window is given up where needed.
-    const int Bsel = selection_batch(lv);   // (the role changes Gs, i.e. the summation split: decided like every other selection)
-    run->role = lv->variant == BANET_BUNDLE && mlp != nullptr && a.use_mlp && syrk_runs_mlp_role(pl.s) && lv->C <= 256 &&
-                (lv->C & 3) == 0 && ((long long)Bsel * (pl.s.Gs + 1) <= num_cus() || (Bsel <= 8 && pl.s.Gs >= 16) ||
-                 (lv->N <= kRoleSmallLevel && pl.s.Gs >= 4)) &&
-                !(lv->flags & kDevMlpInSolve);   // MLP inside the solve kernel (A/B)
-    if (run->role) {
-      a.mlp_y = w.mlp_y;
-      if ((long long)Bsel * (pl.s.Gs + 1) > num_cus()) pl.s.Gs -= 1;
-    }
+    // the lambda MLP as a role workgroup of the SYRK launch, off the solve kernel's critical path: plan_syrk_role (plan.hpp)
+    run->role = plan_syrk_role(pl.s, lv->variant == BANET_BUNDLE && mlp != nullptr && a.use_mlp, selection_batch(lv), lv->N, lv->C,
+                               lv->flags, num_cus());
+    if (run->role.on) a.mlp_y = w.mlp_y;
   }
   return BANET_OK;
 }
@@ -169,14 +155,9 @@ int lm_level_enqueue(const LevelRun& run, hipStream_t s) {
   } else {
     launch_zero_iters(st->iters, lv->B, s);
     if (a.queue) launch_zero_iters(a.queue, lv->B * a.nqueue, s);   // a kernel, not hipMemsetAsync: see prepare_gather
-    const bool role = run.role;
-    const banet_mlp_t* mlp = run.mlp;
     for (int it = 0; it < max_iters; ++it) {
       rc = launch_assemble(lv, pl, st->R, st->T, st->Wc, nullptr, 0, w.partials, w.AtA, w.Atb, w.absres, w.nvalid, s,
-                           a.queue == nullptr, role ? mlp : nullptr, role ? w.mlp_y : nullptr, nullptr,
-                           // fp16 two-piece SYRK: the level's first pass runs the exact form and leaves the basis column maxima
-                           // on the way (no extra pass over the basis); a one-iteration call computes them up front instead
-                           pl.s.f16 ? (it == 0 ? (max_iters > 1 ? 2 : 0) : 1) : -1);
+                           syrk_stats_of_iteration(pl.s, it, max_iters), a.queue == nullptr, &run.role, run.mlp, w.mlp_y);
       if (rc != BANET_OK) return rc;
       {
         RangeScope r("solve", lv->N);
@@ -256,7 +237,7 @@ int banet_ba_assemble_f32(const banet_level_t* lv, const float* R, const float* 
   if (rc != BANET_OK) return rc;
   if (!ws || ws_bytes < pl.ws_bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
   return launch_assemble(lv, pl, R, T, Wc, nullptr, 0, ws, AtA, Atb, absres, nvalid,
-                         static_cast<hipStream_t>(stream), true, nullptr, nullptr, nullptr, pl.s.f16_standalone ? 0 : -1);
+                         static_cast<hipStream_t>(stream), syrk_stats_of_single_pass(pl.s));
 }
 
 int banet_ba_assemble_mask_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc, float* AtA,
@@ -269,8 +250,8 @@ int banet_ba_assemble_mask_f32(const banet_level_t* lv, const float* R, const fl
   rc = plan_assemble(lv, num_cus(), &pl);
   if (rc != BANET_OK) return rc;
   if (!ws || ws_bytes < pl.ws_bytes || !aligned256(ws)) return BANET_ERR_WORKSPACE;
-  return launch_assemble(lv, pl, R, T, Wc, nullptr, 0, ws, AtA, Atb, absres, nvalid, static_cast<hipStream_t>(stream), true,
-                         nullptr, nullptr, mask_out, pl.s.f16_standalone ? 0 : -1);
+  return launch_assemble(lv, pl, R, T, Wc, nullptr, 0, ws, AtA, Atb, absres, nvalid, static_cast<hipStream_t>(stream),
+                         syrk_stats_of_single_pass(pl.s), true, nullptr, nullptr, nullptr, mask_out);
 }
 
 int banet_ba_residual_f32(const banet_level_t* lv, const float* R, const float* T, const float* Wc, const banet_residual_out_t* out,

@@ -150,8 +150,8 @@ int* assemble_queue(const AsmPlan& pl, void* ws) {
 // tags for the profiler: +N = gather kernel at a level with N points, -N = syrk kernel
 int launch_assemble(const banet_level_t* lv, const AsmPlan& pl, const float* R, const float* T, const float* Wc,
                     const int32_t* active, int active_stride, void* ws, float* AtA, float* Atb, float* absres,
-                    float* nvalid, hipStream_t s, bool reset_queue, const banet_mlp_t* role_mlp, float* role_y,
-                    unsigned char* mask_out, int f16_stats) {
+                    float* nvalid, hipStream_t s, SyrkStats stats, bool reset_queue, const SyrkRole* role,
+                    const banet_mlp_t* role_mlp, float* role_y, unsigned char* mask_out) {
   char* base = static_cast<char*>(ws);
   float* gpart = reinterpret_cast<float*>(base);
   float* rec = lv->K > 0 ? reinterpret_cast<float*>(base + pl.off_rec) : nullptr;
@@ -169,11 +169,12 @@ int launch_assemble(const banet_level_t* lv, const AsmPlan& pl, const float* R, 
     RangeScope r("fold", lv->N);
     gred = finish_gather(lv, pl.g, active, active_stride, gpart, s);
   }
+  const SyrkRole rl = (role != nullptr && role->on && role_mlp != nullptr && role_y != nullptr) ? *role : SyrkRole{0, pl.s.Gs};
   if (lv->K > 0) {
     RangeScope r("syrk", lv->N);
     Timed t(s, -lv->N);
     MlpRole mr{};
-    if (role_mlp != nullptr && role_y != nullptr && syrk_runs_mlp_role(pl.s)) {
+    if (rl.on) {
       mr.gpart = gred;
       mr.grows = pl.g.frows;
       mr.gstride = pl.g.pstride;
@@ -183,12 +184,12 @@ int launch_assemble(const banet_level_t* lv, const AsmPlan& pl, const float* R, 
       mr.Nf = (float)lv->N * (float)npairs(lv);
       mr.y = role_y;
     }
-    rc = launch_syrk(lv->basis, rec, lv->B, lv->N, lv->K, npairs(lv), pl.s, active, active_stride, spart, s,
-                     mr.y != nullptr ? &mr : nullptr, f16_stats);
+    rc = launch_syrk(lv->basis, rec, lv->B, lv->N, lv->K, npairs(lv), pl.s, active, active_stride, spart, s, rl,
+                     rl.on ? &mr : nullptr, stats);
     if (rc != BANET_OK) return rc;
   }
   RangeScope r("reduce", lv->N);
-  launch_reduce2(gred, pl.g.frows, pl.g.pstride, spart, pl.s.Gs, pl.s.pstride, active, active_stride, lv->B, lv->K, lv->C,
+  launch_reduce2(gred, pl.g.frows, pl.g.pstride, spart, rl.Gs, pl.s.pstride, active, active_stride, lv->B, lv->K, lv->C,
                  npairs(lv), AtA, Atb, absres, nvalid, s);
   return hipGetLastError() == hipSuccess ? BANET_OK : BANET_ERR_LAUNCH;
 }

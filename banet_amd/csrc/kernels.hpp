@@ -22,7 +22,7 @@ int launch_gather(const banet_level_t* lv, const GatherPlan& pl, const float* R,
 const float* finish_gather(const banet_level_t* lv, const GatherPlan& pl, const int32_t* active, int active_stride,
                            float* partials, hipStream_t s);
 
-// ---- syrk.hip --------------------------------------------------------------------------
+// ---- syrk.hip (driver; the step list: plan.hpp, kernels: syrk_lds / _mfma32 / _bf16x6 / _wide / _stats.hip) -------------
 struct MlpRole {        // one extra workgroup per window of the SYRK launch evaluates the lambda MLP (mlp.hpp); y == nullptr: off
   const float* gpart;   // folded gather partial rows [B * pairs][grows][gstride]
   int grows, gstride;
@@ -31,15 +31,12 @@ struct MlpRole {        // one extra workgroup per window of the SYRK launch eva
   float Nf;             // residual rows per window (N * pairs)
   float* y;             // [B] MLP output
 };
-// (SyrkPlan / plan_syrk / syrk_wide_aux_bytes: plan.hpp)
-int launch_syrk_wide(const float* basis, const float* rec, int B, int N, int K, int pairs, int Gs, int pstride,
-                     const int32_t* active, int active_stride, float* partials, float* aux, hipStream_t s,
-                     const float* colmax = nullptr, const float* recmax = nullptr);   // both given: the fp16 two-piece form
-int launch_syrk(const float* basis, const float* rec, int B, int N, int K, int pairs, const SyrkPlan& pl,
-                const int32_t* active, int active_stride, float* partials, hipStream_t s, const MlpRole* mr = nullptr,
-                int f16_stats = -1);   // f16_stats: -1 = exact bf16 form; 0 / 1 = fp16 two-piece form (pl.f16), basis column maxima to compute / in
-                                       // place; 2 = exact bf16 form that also leaves the column maxima (first iteration of a level)
-inline bool syrk_runs_mlp_role(const SyrkPlan& pl) { return pl.direct == 2; }   // ba_syrk_bf16x6_kernel only
+// (SyrkPlan / plan_syrk / SyrkStats / SyrkRole / plan_syrk_steps: plan.hpp)  Enqueues the steps of plan_syrk_steps.  role: plan_syrk_role's
+// (or {0, pl.Gs}): role.Gs partial rows per window are written; mr: the role's arguments where role.on; stats: which form runs and
+// what becomes of the basis column maxima (syrk_stats_of_iteration / syrk_stats_of_single_pass)
+int launch_syrk(const float* basis, const float* rec, int B, int N, int K, int pairs, const SyrkPlan& pl, const int32_t* active,
+                int active_stride, float* partials, hipStream_t s, const SyrkRole& role, const MlpRole* mr, SyrkStats stats);
+// ---- syrk_reduce.hip ---------------------------------------------------------------------
 void launch_reduce2(const float* gpart, int Gg, int gstride, const float* spart, int Gs, int sstride,
                     const int32_t* active, int active_stride, int B, int K, int C, int pairs, float* AtA, float* Atb,
                     float* absres, float* nvalid, hipStream_t s);
@@ -48,8 +45,9 @@ void launch_reduce2(const float* gpart, int Gg, int gstride, const float* spart,
 // (AsmPlan / plan_assemble: plan.hpp)
 int launch_assemble(const banet_level_t* lv, const AsmPlan& pl, const float* R, const float* T, const float* Wc,
                     const int32_t* active, int active_stride, void* ws, float* AtA, float* Atb, float* absres,
-                    float* nvalid, hipStream_t s, bool reset_queue = true, const banet_mlp_t* role_mlp = nullptr,
-                    float* role_y = nullptr, unsigned char* mask_out = nullptr, int f16_stats = -1);
+                    float* nvalid, hipStream_t s, SyrkStats stats = kSyrkStatsExact, bool reset_queue = true,
+                    const SyrkRole* role = nullptr, const banet_mlp_t* role_mlp = nullptr, float* role_y = nullptr,
+                    unsigned char* mask_out = nullptr);   // role (with role_mlp / role_y): plan_syrk_role's, where it is on
 int* assemble_queue(const AsmPlan& pl, void* ws);   // the gather's tile-queue heads inside the workspace (or nullptr)
 int profile_ranges(int enable);             // roctx ranges around the launches (banet_profile_ranges)
 struct RangeScope {                         // pushes "banet.<role>[ N=<n>]" when ranges are on
@@ -257,7 +255,7 @@ struct LevelRun {   // what lm_level_plan decided; host memory only
   SolveArgs a;
   int max_iters;
   bool lm;     // device-side loop control (BANET_LEGACY_LM with early termination)
-  bool role;   // the lambda MLP runs as a role workgroup of the SYRK launch
+  SyrkRole role;   // role.on: the lambda MLP runs as a role workgroup of the SYRK launch, on role.Gs partial rows per window
 };
 // every check of banet_lm_level_ex_f32, in its order and with its return codes; launches nothing
 int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, int early_termination,

@@ -1,7 +1,9 @@
 // The host-side launch plans of one assembly pass: which gather / SYRK kernel runs, on what grid, how many partial rows it
-// writes (the summation tree) and where every buffer lies in the workspace.  Host-only, plain C++17 (no HIP include): the .hip
-// files take the plans AND the occupancy numbers of their __launch_bounds__ from here, and tests/native/plan_host.cpp
-// compiles this header with g++ to pin every decision (tests/test_plan_cpu.py).
+// writes (the summation tree) and where every buffer lies in the workspace; for the SYRK also every launch of a pass as a list of
+// steps (plan_syrk_steps: pre-passes, kernel instantiation, job, grid, LDS -- syrk.hip walks it), the statistics mode of a pass
+// (SyrkStats), the lambda-MLP role decision (plan_syrk_role) and the lists of compiled SYRK instantiations.  Host-only, plain C++17
+// (no HIP include): the .hip files take the plans AND the occupancy numbers of their __launch_bounds__ from here, and
+// tests/native/plan_host.cpp compiles this header with g++ to pin every decision (tests/test_plan_cpu.py, tests/test_syrk_steps_cpu.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -254,15 +256,20 @@ inline int plan_gather(const banet_level_t* lv, int kCUs, GatherPlan* pl) {
 }
 
 // ---- syrk ------------------------------------------------------------------------------
+enum SyrkKind {          // SyrkPlan.direct
+  kSyrkLds = 0,          // the LDS-tiled kernel (syrk_lds.hip), any K <= 256
+  kSyrkMfma32 = 1,       // ba_syrk_direct_kernel (syrk_mfma32.hip: fp32 MFMA, A/B only)
+  kSyrkBf16x6 = 2,       // ba_syrk_bf16x6_kernel (syrk_bf16x6.hip: K = 64 / 128, <= 4 target frames)
+  kSyrkWide = 3,         // the jobs of syrk_wide.hip (K = 256, or K = 128 with more than 4 target frames)
+};
 struct SyrkPlan {
   int Gs, tiles, pstride, nb;
   int x3;       // ba_syrk_bf16x6_kernel, opt-in: three products instead of six (kDevSyrkThreeProducts)
-  int direct;   // 0: the LDS-tiled kernel, 1: ba_syrk_direct_kernel (fp32 MFMA, A/B), 2: ba_syrk_bf16x6_kernel (K = 64 / 128, <= 4 frames),
-                // 3: syrk_wide.hip jobs (K = 256, or K = 128 with more than 4 target frames)
+  int direct;   // SyrkKind
   int f16;      // ba_syrk_bf16x6_kernel: the fp16 two-piece form is eligible (plan_syrk); f16_standalone: also in a single assembly pass
   int f16_standalone;
   size_t off_colmax, off_recmax;   // f16: [B][K] basis column maxima, [B][32][2] record maxima, inside the partial buffer
-  size_t off_aux;        // direct == 3: per-pixel (s, r) sums over the frames, inside the partial buffer
+  size_t off_aux;        // kSyrkWide: per-pixel (s, r) sums over the frames, inside the partial buffer
   size_t partial_bytes;
 };
 
@@ -286,15 +293,15 @@ inline int plan_syrk(int B, int Bsel, int N, int K, int pairs, int flags, int cu
   if (pl->nb < 0) return BANET_ERR_UNSUPPORTED;
   if (K == 0) return BANET_OK;   // no depth block: nothing runs
   pl->tiles = (N + kTilePix - 1) / kTilePix;
-  // K = 64 / 128: barrier-free kernels, one wave per SIMD, one workgroup per CU in all: 2 = ba_syrk_bf16x6_kernel
-  // (default), 1 = ba_syrk_direct_kernel (fp32 MFMA; kDevSyrkNoBf16x6, A/B only)
-  pl->direct = ((K == 64 || K == 128) && pairs <= 4) ? ((flags & kDevSyrkNoBf16x6) ? 1 : 2) : 0;
+  // K = 64 / 128: barrier-free kernels, one wave per SIMD, one workgroup per CU in all: ba_syrk_bf16x6_kernel
+  // (default) or ba_syrk_direct_kernel (fp32 MFMA; kDevSyrkNoBf16x6, A/B only)
+  pl->direct = ((K == 64 || K == 128) && pairs <= 4) ? ((flags & kDevSyrkNoBf16x6) ? kSyrkMfma32 : kSyrkBf16x6) : kSyrkLds;
   // OPT-IN (kDevSyrkThreeProducts, K = 128): the three largest of the six products only -- a two-piece split, 16 significand bits per
   // operand, ~2^-16 relative error per product instead of 2^-24.  Not the product path and not what bench.py's `value` is measured
   // with (its dtype is "f32": fp32-exact products); measured beside it: profiles/r03_run31_*, DESIGN.md section 7.
-  pl->x3 = (pl->direct == 2 && K == 128 && (flags & kDevSyrkThreeProducts)) ? 1 : 0;
+  pl->x3 = (pl->direct == kSyrkBf16x6 && K == 128 && (flags & kDevSyrkThreeProducts)) ? 1 : 0;
   // K = 256, or K = 128 with more than 4 target frames: the job kernels of syrk_wide.hip (kDevSyrkNoBf16x6: the LDS-tiled kernel, A/B)
-  if (!(flags & kDevSyrkNoBf16x6) && (K == 256 || (K == 128 && pairs > 4))) pl->direct = 3;
+  if (!(flags & kDevSyrkNoBf16x6) && (K == 256 || (K == 128 && pairs > 4))) pl->direct = kSyrkWide;
   int target = (((pl->direct || pl->nb > 8) ? cus : 2 * cus) + Bsel - 1) / Bsel;   // Gs = partial rows per window: part of the arithmetic, hence from Bsel   // LDS kernel: 2 resident workgroups per CU (1 at K > 128)
   int G = pl->direct ? (N + 4 * 4 * 16 - 1) / (4 * 4 * 16) : pl->tiles / 4;   // direct: >= 16 quads per wave
   if (G > target) G = target;
@@ -303,18 +310,189 @@ inline int plan_syrk(int B, int Bsel, int N, int K, int pairs, int flags, int cu
   pl->pstride = (int)align_up((size_t)(6 * pairs + 1) * K + (size_t)K * K, 4);
   pl->partial_bytes = align_up((size_t)B * G * pl->pstride * sizeof(float), 256);
   pl->off_aux = pl->partial_bytes;
-  if (pl->direct == 3) pl->partial_bytes += syrk_wide_aux_bytes(B, N, pairs);
+  if (pl->direct == kSyrkWide) pl->partial_bytes += syrk_wide_aux_bytes(B, N, pairs);
   // The fp16 two-piece form of ba_syrk_bf16x6_kernel (half the MFMAs, 5 instead of 9 split instructions per two values, the same
   // accuracy class: ~2^-21 per product against the reference's fp32 GEMM) where the launch is throughput-bound -- at least
   // kSyrkF16Pixels pixels in all -- so that its two small pre-passes (basis column maxima once per level, record maxima per pass)
   // are noise.  LM loop (banet_lm_level_f32) only; the single assembly pass keeps the exact bf16 form unless kDevSyrkF16 asks
   // for this one (tests).  kDevNoSyrkF16: never (A/B).
-  pl->f16 = ((pl->direct == 2 || pl->direct == 3) && !pl->x3 && !(flags & kDevNoSyrkF16) && ((long long)N * Bsel >= kSyrkF16Pixels || (flags & kDevSyrkF16))) ? 1 : 0;
+  pl->f16 = ((pl->direct == kSyrkBf16x6 || pl->direct == kSyrkWide) && !pl->x3 && !(flags & kDevNoSyrkF16) && ((long long)N * Bsel >= kSyrkF16Pixels || (flags & kDevSyrkF16))) ? 1 : 0;
   pl->f16_standalone = (pl->f16 && (flags & kDevSyrkF16)) ? 1 : 0;
   pl->off_colmax = pl->partial_bytes;
   pl->off_recmax = pl->off_colmax + (pl->f16 ? align_up((size_t)B * K * sizeof(float), 256) : 0);
   if (pl->f16) pl->partial_bytes = pl->off_recmax + align_up((size_t)B * kRecMaxBlocks * 2 * sizeof(float), 256);
   return BANET_OK;
+}
+
+// ---- the SYRK launch as data ---------------------------------------------------------------
+// What syrk.hip enqueues for one pass: plan_syrk_steps lists every launch -- pre-passes included -- in order, with its kernel,
+// template parameters, job, grid and LDS; the driver walks the list and decides nothing (tests/native/plan_host.cpp dumps it,
+// tests/test_syrk_steps_cpu.py pins it).
+
+// The column maxima of the fp16 two-piece form in one pass of a level (the basis does not change within a level)
+enum SyrkStats {
+  kSyrkStatsExact = -1,         // the exact bf16 form
+  kSyrkStatsF16Compute = 0,     // the fp16 form; compute the basis column maxima now
+  kSyrkStatsF16InPlace = 1,     // the fp16 form; the maxima are in place
+  kSyrkStatsExactHarvest = 2,   // the exact form that also leaves the maxima (first iteration of a level)
+};
+// iteration `it` of a level's LM loop: the first pass runs the exact form and leaves the maxima on the way (no extra pass over the
+// basis), the later ones the fp16 form with them; a one-iteration call computes them up front instead
+inline SyrkStats syrk_stats_of_iteration(const SyrkPlan& pl, int it, int max_iters) {
+  if (!pl.f16) return kSyrkStatsExact;
+  if (it > 0) return kSyrkStatsF16InPlace;
+  return max_iters > 1 ? kSyrkStatsExactHarvest : kSyrkStatsF16Compute;
+}
+// a single assembly pass: the exact form unless kDevSyrkF16 asks for the fp16 one
+inline SyrkStats syrk_stats_of_single_pass(const SyrkPlan& pl) { return pl.f16_standalone ? kSyrkStatsF16Compute : kSyrkStatsExact; }
+
+// The lambda MLP as a role workgroup of the SYRK launch (ba_syrk_bf16x6_kernel only: one more workgroup per window, hidden behind
+// the SYRK workgroups, off the solve kernel's critical path; C <= 256: the role's LDS scratch)
+// ... and coarse levels at any batch (N <= kRoleSmallLevel pixels: their SYRK is a latency chain of 1-3 steps per wave, so a
+// window's 7 workgroups take what 8 take, and the solve kernel loses the 19 us MLP: 40x30 .. 160x120 x 32 windows).
+// Small batches only (B <= 8) otherwise: the SYRK kernel runs one workgroup per CU (512 registers per wave), so the role workgroups
+// need CUs of their own -- at B = 32 (8 + 1 workgroups per window = 288 > 256 CUs) a second round of workgroups doubled
+// the SYRK time (640x480 x 32: 1326 -> 2457 us); with B <= 8 one SYRK workgroup per window is given up where needed.
+constexpr int kRoleSmallLevel = 19200;   // pixels: levels whose SYRK launch is latency-bound
+struct SyrkRole {
+  int on;
+  int Gs;   // partial rows per window to launch and reduce with: pl.Gs, or one fewer (the workspace stays sized from pl.Gs)
+};
+// bundle_mlp: a bundle level whose damping comes from the lambda MLP; Bsel: selection_batch (the role changes Gs, i.e. the
+// summation split: decided like every other selection); flags: banet_level_t.flags (kDevMlpInSolve: MLP inside the solve kernel, A/B)
+inline SyrkRole plan_syrk_role(const SyrkPlan& pl, bool bundle_mlp, int Bsel, int N, int C, int flags, int cus) {
+  const bool on = bundle_mlp && pl.direct == kSyrkBf16x6 && C <= 256 && (C & 3) == 0 &&
+                  ((long long)Bsel * (pl.Gs + 1) <= cus || (Bsel <= 8 && pl.Gs >= 16) || (N <= kRoleSmallLevel && pl.Gs >= 4)) &&
+                  !(flags & kDevMlpInSolve);
+  return SyrkRole{on ? 1 : 0, (on && (long long)Bsel * (pl.Gs + 1) > cus) ? pl.Gs - 1 : pl.Gs};
+}
+
+// The compiled instantiations, each list written once: the launchers instantiate from these lists, plan_syrk_steps takes
+// "supported" from them and the host test program enumerates them.
+#define BANET_SYRK_LDS_LIST(X) X(1) X(2) X(4) X(8) X(16)       // ba_syrk_kernel<NB>
+#define BANET_SYRK_FRAMES_LIST(X) X(1) X(2) X(3) X(4)          // PAIRS of the two register kernels, PT of the slice jobs: crossed with
+#define BANET_SYRK_MFMA32_LIST(X) X(1) X(2)                    // ba_syrk_direct_kernel<KH, PAIRS>: KH
+#define BANET_SYRK_BF16X6_LIST(X) X(1, 0) X(1, 1) X(1, 16) X(2, 0) X(2, 1) X(2, 3) X(2, 16)   // ba_syrk_bf16x6_kernel<KH, PAIRS, T0>: (KH, T0)
+#define BANET_SYRK_SLICE_LIST(X) X(true, false) X(true, true) X(false, false) X(false, true)   // ba_syrk_slice_kernel<PT, DD, F16>: (DD, F16)
+#define BANET_SYRK_RECT_LIST(X) X(false) X(true)               // ba_syrk_rect_kernel<F16>
+
+enum SyrkStepKind {
+  kSyrkStepZero = 0,   // zero_iters_kernel on the column maxima (j0 words)
+  kSyrkStepColmax,     // ba_colmax_kernel
+  kSyrkStepRecmax,     // ba_recmax_kernel
+  kSyrkStepSrsum,      // ba_srsum_kernel
+  kSyrkStepLds,        // ba_syrk_kernel<t0 = NB>, job j0 = pass
+  kSyrkStepMfma32,     // ba_syrk_direct_kernel<t0 = KH, t1 = PAIRS>
+  kSyrkStepBf16x6,     // ba_syrk_bf16x6_kernel<t0 = KH, t1 = PAIRS, t2 = T0>
+  kSyrkStepSlice,      // ba_syrk_slice_kernel<t0 = PT, t1 = DD, t2 = F16>, job j0 = koff, j1 = p0
+  kSyrkStepRect,       // ba_syrk_rect_kernel<t0 = F16>, job j0 = r0, j1 = c0
+};
+struct SyrkStep {
+  int kind;           // SyrkStepKind
+  int t0, t1, t2;     // template parameters
+  int j0, j1;         // job parameters
+  int gx, gy, block;
+  int lds;            // dynamic LDS bytes
+  int lds_attr;       // 1: more than 64 KB, the launch sets the function attribute
+};
+// The project's largest windows (8 target frames) need 10: zero, colmax, recmax, srsum, four slices, two rectangles at K = 256.  The
+// API does not bound the frames of a window, and the LDS-tiled kernel takes one pass per frame: the list holds up to 64 frames in
+// every form (wide jobs: 4 + 2 x 16 + 2); beyond that plan_syrk_steps refuses.
+constexpr int kSyrkMaxSteps = 64;
+struct SyrkSteps {
+  int n;
+  SyrkStep step[kSyrkMaxSteps];
+};
+
+namespace plan_detail {
+
+inline bool syrk_step_compiled(const SyrkStep& st) {
+  bool frames = false, found = false;
+#define BANET_X(p) frames = frames || (st.kind == kSyrkStepSlice ? st.t0 : st.t1) == p;
+  BANET_SYRK_FRAMES_LIST(BANET_X)
+#undef BANET_X
+  switch (st.kind) {
+    case kSyrkStepLds:
+#define BANET_X(nb) found = found || st.t0 == nb;
+      BANET_SYRK_LDS_LIST(BANET_X)
+#undef BANET_X
+      return found;
+    case kSyrkStepMfma32:
+#define BANET_X(kh) found = found || st.t0 == kh;
+      BANET_SYRK_MFMA32_LIST(BANET_X)
+#undef BANET_X
+      return found && frames;
+    case kSyrkStepBf16x6:
+#define BANET_X(kh, t) found = found || (st.t0 == kh && st.t2 == t);
+      BANET_SYRK_BF16X6_LIST(BANET_X)
+#undef BANET_X
+      return found && frames;
+    case kSyrkStepSlice:
+#define BANET_X(dd, f16) found = found || (st.t1 == (dd ? 1 : 0) && st.t2 == (f16 ? 1 : 0));
+      BANET_SYRK_SLICE_LIST(BANET_X)
+#undef BANET_X
+      return found && frames;
+    case kSyrkStepRect:
+#define BANET_X(f16) found = found || st.t0 == (f16 ? 1 : 0);
+      BANET_SYRK_RECT_LIST(BANET_X)
+#undef BANET_X
+      return found;
+  }
+  return true;   // the pre-passes are not templates
+}
+
+// appends a step on (gx, B) workgroups; false where the list is full or the instantiation is not compiled
+inline bool syrk_push(SyrkSteps* out, int kind, int t0, int t1, int t2, int j0, int j1, int gx, int gy, int block, size_t lds = 0) {
+  const SyrkStep st{kind, t0, t1, t2, j0, j1, gx, gy, block, (int)lds, lds > 64 * 1024 ? 1 : 0};
+  if (out->n >= kSyrkMaxSteps || !syrk_step_compiled(st)) return false;
+  out->step[out->n++] = st;
+  return true;
+}
+
+}  // namespace plan_detail
+
+// The launches of one SYRK pass, in order.  pl: plan_syrk's; cus: as plan_gather's kCUs; role: plan_syrk_role's, or {0, pl.Gs}.
+// BANET_ERR_UNSUPPORTED (and an empty list) where a step has no compiled kernel: nb outside BANET_SYRK_LDS_LIST (K = 0 among
+// them: launch_assemble does not call the SYRK then), wide jobs at K other than 128 or 256.
+inline int plan_syrk_steps(const SyrkPlan& pl, int B, int N, int K, int pairs, int cus, SyrkStats stats, const SyrkRole& role, SyrkSteps* out) {
+  using namespace plan_detail;
+  *out = SyrkSteps{};
+  const int Gs = role.Gs;
+  bool ok = true;
+  if (pl.direct == kSyrkBf16x6 || pl.direct == kSyrkWide) {
+    if (pl.direct == kSyrkWide && K != 128 && K != 256) return BANET_ERR_UNSUPPORTED;
+    const bool maxima = pl.f16 && stats != kSyrkStatsExact;
+    // THE difference between the two: ba_syrk_bf16x6_kernel<.., .., 1> harvests the column maxima while it runs the exact form; the
+    // wide jobs have no such variant, so "exact form that also leaves the maxima" is, for them, a colmax pass plus the fp16 form
+    // already on that iteration
+    const bool harvest = maxima && stats == kSyrkStatsExactHarvest && pl.direct == kSyrkBf16x6;
+    const bool f16 = maxima && !harvest;
+    const bool colmax = f16 && stats != kSyrkStatsF16InPlace;
+    if (harvest || colmax) ok = ok && syrk_push(out, kSyrkStepZero, 0, 0, 0, B * K, 0, (B * K + 63) / 64, 1, 64);
+    if (colmax) ok = ok && syrk_push(out, kSyrkStepColmax, 0, 0, 0, 0, 0, std::max(1, std::min((N + 255) / 256, (8 * cus + B - 1) / B)), B, 256);
+    if (f16) ok = ok && syrk_push(out, kSyrkStepRecmax, 0, 0, 0, 0, 0, kRecMaxBlocks, B, 256);
+    if (pl.direct == kSyrkBf16x6) {
+      const int T0 = harvest ? 1 : f16 ? 16 : pl.x3 ? 3 : 0;
+      ok = ok && syrk_push(out, kSyrkStepBf16x6, K / 64, pairs, T0, 0, 0, Gs + role.on, B, kBlock);
+    } else {
+      // s and r summed over the window's frames by a small pre-pass, so that the jobs do not depend on the number of frames
+      if (pairs > 1) ok = ok && syrk_push(out, kSyrkStepSrsum, 0, 0, 0, 0, 0, (N + 255) / 256, B, 256);
+      for (int koff = 0; koff < K; koff += 128)        // the symmetric 128 x 128 diagonal slices, H_cd of up to 4 frames each
+        for (int p0 = 0; p0 < pairs; p0 += 4)
+          ok = ok && syrk_push(out, kSyrkStepSlice, std::min(pairs - p0, 4), p0 == 0 ? 1 : 0, f16 ? 1 : 0, koff, p0, Gs, B, kBlock);
+      for (int r0 = 0; r0 < K; r0 += 128)              // off-diagonal 128 x 64 rectangles above the diagonal slices
+        for (int c0 = r0 + 128; c0 < K; c0 += 64) ok = ok && syrk_push(out, kSyrkStepRect, f16 ? 1 : 0, 0, 0, r0, c0, Gs, B, kBlock);
+    }
+  } else if (pl.direct == kSyrkMfma32) {
+    ok = syrk_push(out, kSyrkStepMfma32, K / 64, pairs, 0, 0, 0, Gs, B, kBlock);
+  } else {
+    // LDS-tiled kernel: one pass per pair (H_dd / Atb_d in pass 0); [2][64][KP] basis rows + [2][64][8] records, or the epilogue's [4][8][KPAD]
+    const size_t KPAD = (size_t)pl.nb * 16, KP = KPAD + 16;
+    const size_t lds = std::max((size_t)2 * kTilePix * KP + 2 * kTilePix * 8, (size_t)4 * 8 * KPAD) * sizeof(float);
+    for (int pass = 0; pass < pairs; ++pass) ok = ok && syrk_push(out, kSyrkStepLds, pl.nb, 0, 0, pass, 0, Gs, B, kBlock, lds);
+  }
+  if (!ok) *out = SyrkSteps{};
+  return ok ? BANET_OK : BANET_ERR_UNSUPPORTED;
 }
 
 // ---- one assembly pass = gather + syrk + reduce -----------------------------------------

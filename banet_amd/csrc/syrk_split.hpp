@@ -1,4 +1,4 @@
-// bf16x3 operand split shared by the bf16x6 SYRK kernels (syrk.hip, syrk_wide.hip).
+// bf16x3 operand split shared by the bf16x6 SYRK kernels (syrk_bf16x6.hip, syrk_wide.hip) and the other users of the scheme.
 #pragma once
 #include <hip/hip_runtime.h>
 

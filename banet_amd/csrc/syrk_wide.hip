@@ -1,6 +1,6 @@
 // syrk_wide.hip -- the depth blocks of the normal equations for wide bases / many frames on the bf16 matrix pipe:
 //   K = 256 (any number of target frames) and K = 128 with more than 4 target frames.
-// Same arithmetic as ba_syrk_bf16x6_kernel (syrk.hip): v = sqrt(s) b split exactly into three bf16 pieces, six
+// Same arithmetic as ba_syrk_bf16x6_kernel (syrk_bf16x6.hip): v = sqrt(s) b split exactly into three bf16 pieces, six
 // v_mfma_f32_16x16x32_bf16 per 16x16 block and 32 pixels, H_cd / Atb_d through u / sqrt(s).  A wave cannot hold the
 // 136 upper blocks of a 256 x 256 matrix (544 accumulator registers), so the matrix is cut into JOBS, each one pass
 // over the pixels with the accumulators resident in registers (one wave per SIMD, no LDS, no barrier in the loop):
@@ -10,85 +10,27 @@
 // K = 256, 7 target frames: slice(0,0,DD) slice(0,4) slice(128,0,DD) slice(128,4) rect(0,128) rect(0,192) = 3.5 reads
 // of the basis, against 7 passes (one per frame) of the LDS-tiled fp32 kernel it replaces (utils.cu:331-414 is the
 // reference's materialised form of the same sums).  s and r summed over the window's frames come from a small pre-pass
-// (ba_srsum_kernel, 8 bytes per pixel) so that the jobs do not depend on the number of frames.
+// (ba_srsum_kernel of syrk_stats.hip, 8 bytes per pixel) so that the jobs do not depend on the number of frames.  Which jobs a
+// level runs: plan_syrk_steps (plan.hpp).
 // Partial layout = the other SYRK kernels' ([B][Gs][(6 pairs + 1) K + K K]): ba_reduce2_kernel is unchanged.
-#include "kernels.hpp"
-#include "syrk_split.hpp"
+#include "syrk_common.hpp"
 
 namespace banet {
-
-typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-
-struct WideArgs {
-  const float* basis;  // [B][N][K]
-  const float* rec;    // [B][pairs][N][8]
-  const float* srsum;  // [B][N][2] (s, r summed over the frames) or nullptr when pairs == 1 (then rec words 6, 7)
-  const int32_t* active;
-  int active_stride;
-  float* partials;
-  int N, K, Gs, pstride, pairs;
-  int koff, p0;        // slice job
-  int r0, c0;          // rect job
-  const float* colmax; // F16 (the fp16 two-piece form, see syrk.hip): [B][K] max_n |b_nk|
-  const float* recmax; // F16: [B][kWideRecMaxBlocks][2] per-block max s_n, max word^2 / s_n (ba_recmax_kernel, syrk.hip)
-};
-constexpr int kWideRecMaxBlocks = 32;    // = kRecMaxBlocks of syrk.hip
-typedef _Float16 f16x8w __attribute__((ext_vector_type(8)));
 
 // fp16 two-piece products, smallest first: lo hi' + hi lo' + hi hi'
 __device__ __forceinline__ f32x4 mm3(const u32x4_t (&x)[2], const u32x4_t (&y)[2], f32x4 c) {
   constexpr int kFa[3] = {1, 0, 0}, kFb[3] = {0, 1, 0};
 #pragma unroll
   for (int t = 0; t < 3; ++t)
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8w, x[kFa[t]]), __builtin_bit_cast(f16x8w, y[kFb[t]]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, x[kFa[t]]), __builtin_bit_cast(f16x8, y[kFb[t]]), c, 0, 0, 0);
   return c;
-}
-
-// the window's record maxima -> (2^es > sqrt(max s), 2^eu > sqrt(max word^2 / s)); false if they are not finite
-__device__ __forceinline__ bool wide_rec_exponents(const float* recmax, int b, int lane, int& es, int& eu) {
-  float smx = 0.f, wmx = 0.f;
-  if (lane < kWideRecMaxBlocks) {
-    smx = recmax[((size_t)b * kWideRecMaxBlocks + lane) * 2];
-    wmx = recmax[((size_t)b * kWideRecMaxBlocks + lane) * 2 + 1];
-  }
-#pragma unroll
-  for (int sh = 1; sh < 64; sh <<= 1) {
-    smx = fmaxf(smx, __shfl_xor(smx, sh, 64));
-    wmx = fmaxf(wmx, __shfl_xor(wmx, sh, 64));
-  }
-  (void)frexpf(sqrtf(smx), &es);
-  (void)frexpf(sqrtf(wmx), &eu);
-  return (smx < __builtin_inff()) && (wmx < __builtin_inff()) && !(smx != smx) && !(wmx != wmx);
-}
-// column scale 2^(14 - ek - es) for max |b| = cm < 2^ek; ok &= representable
-__device__ __forceinline__ float wide_col_scale(float cm, int es, bool& ok, float& inv) {
-  int ek = 0;
-  (void)frexpf(cm, &ek);
-  const int sh = 14 - ek - es;
-  ok = ok && (cm < __builtin_inff()) && !(cm != cm) && sh > -100 && sh < 100;
-  inv = ldexpf(1.f, -sh);
-  return ldexpf(1.f, sh);
-}
-
-__global__ __launch_bounds__(256) void ba_srsum_kernel(const float* __restrict__ rec, int N, int pairs,
-                                                       const int32_t* active, int active_stride, float* __restrict__ out) {
-  const int b = blockIdx.y, n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (active != nullptr && active[(size_t)b * active_stride] == 0) return;
-  if (n >= N) return;
-  float s = 0.f, r = 0.f;
-  for (int p = 0; p < pairs; ++p) {   // fixed order
-    const float2 v = *reinterpret_cast<const float2*>(rec + (((size_t)b * pairs + p) * N + n) * 8 + 6);
-    s += v.x;
-    r += v.y;
-  }
-  *reinterpret_cast<float2*>(out + ((size_t)b * N + n) * 2) = make_float2(s, r);
 }
 
 __device__ __forceinline__ f32x4 mm6(const u32x4_t (&x)[3], const u32x4_t (&y)[3], f32x4 c) {
   constexpr int kTa[6] = {2, 0, 1, 1, 0, 0}, kTb[6] = {0, 2, 1, 0, 1, 0};   // smallest terms first
 #pragma unroll
   for (int t = 0; t < 6; ++t)
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8w, x[kTa[t]]), __builtin_bit_cast(bf16x8w, y[kTb[t]]), c, 0, 0,
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x[kTa[t]]), __builtin_bit_cast(bf16x8, y[kTb[t]]), c, 0, 0,
                                                 0);
   return c;
 }
@@ -143,14 +85,14 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_slice_kernel(const WideArgs
   const int ns = (N + 31) >> 5, nwaves = a.Gs * kNumWaves, gw = g * kNumWaves + w;
   const int s0 = (int)(((long long)ns * gw) / nwaves), s1 = (int)(((long long)ns * (gw + 1)) / nwaves);
 
-  // F16: per-column power-of-two scales of this slice's 128 columns + one for the record rows (syrk.hip, T0 = 16)
+  // F16: per-column power-of-two scales of this slice's 128 columns + one for the record rows (syrk_bf16x6.hip, T0 = 16)
   [[maybe_unused]] float csc[4 * KH];
   [[maybe_unused]] float usc = 1.f, uinv = 1.f;
   [[maybe_unused]] bool use16 = false;
   [[maybe_unused]] __shared__ float sInv[64 * KH];
   if constexpr (F16) {
     int es = 0, eu = 0;
-    bool ok = wide_rec_exponents(a.recmax, b, lane, es, eu);
+    bool ok = f16_rec_exponents(a.recmax, b, lane, es, eu);
     usc = ldexpf(1.f, 14 - eu);
     uinv = ldexpf(1.f, eu - 14);
 #pragma unroll
@@ -159,7 +101,7 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_slice_kernel(const WideArgs
       for (int e = 0; e < 4; ++e) {
         const int col = 64 * h + 4 * m + e;
         float inv;
-        csc[4 * h + e] = wide_col_scale(a.colmax[(size_t)b * K + a.koff + col], es, ok, inv);
+        csc[4 * h + e] = f16_col_scale(a.colmax[(size_t)b * K + a.koff + col], es, ok, inv);
         if (w == 0 && kq == 0) sInv[col] = inv;
       }
     use16 = __ballot(!ok) == 0ull;
@@ -238,7 +180,7 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_slice_kernel(const WideArgs
       for (int i = 0; i < 8; ++i) {
         const bool ok = 32 * st + 8 * kq + i < N;
         sq[i] = ok ? sqrtf(fmaxf(ps[i], 0.f)) : 0.f;            // zero switches the pixel off
-        const float inv = sq[i] > 0.f ? 1.f / sq[i] : 0.f;      // s = 0 implies u = r = 0 (syrk.hip)
+        const float inv = sq[i] > 0.f ? 1.f / sq[i] : 0.f;      // s = 0 implies u = r = 0 (syrk_bf16x6.hip)
 #pragma unroll
         for (int j = 0; j < NU; ++j) ut[j][i] = uon[j] ? pu[i][j] * inv : 0.f;
       }
@@ -369,20 +311,20 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_rect_kernel(const WideArgs 
   [[maybe_unused]] __shared__ float sInvR[128], sInvC[64];
   if constexpr (F16) {
     int es = 0, eu = 0;
-    bool ok = wide_rec_exponents(a.recmax, b, lane, es, eu);
+    bool ok = f16_rec_exponents(a.recmax, b, lane, es, eu);
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int col = 64 * h + 4 * m + e;
         float inv;
-        cscr[4 * h + e] = wide_col_scale(a.colmax[(size_t)b * K + a.r0 + col], es, ok, inv);
+        cscr[4 * h + e] = f16_col_scale(a.colmax[(size_t)b * K + a.r0 + col], es, ok, inv);
         if (w == 0 && kq == 0) sInvR[col] = inv;
       }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float inv;
-      cscc[e] = wide_col_scale(a.colmax[(size_t)b * K + a.c0 + 4 * m + e], es, ok, inv);
+      cscc[e] = f16_col_scale(a.colmax[(size_t)b * K + a.c0 + 4 * m + e], es, ok, inv);
       if (w == 0 && kq == 0) sInvC[4 * m + e] = inv;
     }
     use16 = __ballot(!ok) == 0ull;
@@ -489,49 +431,37 @@ __global__ __launch_bounds__(kBlock, 1) void ba_syrk_rect_kernel(const WideArgs 
 }
 
 template <bool DD, bool F16>
-static void launch_slice(const WideArgs& a, int B, int pt, hipStream_t s) {
-  const dim3 grid(a.Gs, B), block(kBlock);
-  switch (pt) {
-    case 1: hipLaunchKernelGGL((ba_syrk_slice_kernel<1, DD, F16>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((ba_syrk_slice_kernel<2, DD, F16>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((ba_syrk_slice_kernel<3, DD, F16>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((ba_syrk_slice_kernel<4, DD, F16>), grid, block, 0, s, a); break;
+static int launch_slice(const SyrkStep& st, const WideArgs& a, hipStream_t s) {
+  const dim3 grid(st.gx, st.gy), block(st.block);
+  switch (st.t0) {
+#define BANET_X(pt) \
+  case pt: hipLaunchKernelGGL((ba_syrk_slice_kernel<pt, DD, F16>), grid, block, 0, s, a); return BANET_OK;
+    BANET_SYRK_FRAMES_LIST(BANET_X)
+#undef BANET_X
   }
+  return BANET_ERR_UNSUPPORTED;
 }
 
-
-int launch_syrk_wide(const float* basis, const float* rec, int B, int N, int K, int pairs, int Gs, int pstride,
-                     const int32_t* active, int active_stride, float* partials, float* aux, hipStream_t s, const float* colmax,
-                     const float* recmax) {
-  if (K != 128 && K != 256) return BANET_ERR_UNSUPPORTED;
-  const bool f16 = colmax != nullptr && recmax != nullptr;       // the fp16 two-piece form (scales prepared by launch_syrk)
-  WideArgs a{basis, rec, nullptr, active, active_stride, partials, N, K, Gs, pstride, pairs, 0, 0, 0, 0, colmax, recmax};
-  if (pairs > 1) {
-    hipLaunchKernelGGL(ba_srsum_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, rec, N, pairs, active, active_stride, aux);
-    a.srsum = aux;
+int launch_syrk_wide_step(const SyrkStep& st, WideArgs a, hipStream_t s) {
+  if (st.kind == kSyrkStepSlice) {
+    a.koff = st.j0;
+    a.p0 = st.j1;
+#define BANET_X(dd, f16) \
+  if (st.t1 == (dd ? 1 : 0) && st.t2 == (f16 ? 1 : 0)) return launch_slice<dd, f16>(st, a, s);
+    BANET_SYRK_SLICE_LIST(BANET_X)
+#undef BANET_X
+    return BANET_ERR_UNSUPPORTED;
   }
-  for (int koff = 0; koff < K; koff += 128) {
-    a.koff = koff;
-    for (int p0 = 0; p0 < pairs; p0 += 4) {
-      a.p0 = p0;
-      const int pt = pairs - p0 < 4 ? pairs - p0 : 4;
-      if (p0 == 0) {
-        if (f16) launch_slice<true, true>(a, B, pt, s);
-        else launch_slice<true, false>(a, B, pt, s);
-      } else {
-        if (f16) launch_slice<false, true>(a, B, pt, s);
-        else launch_slice<false, false>(a, B, pt, s);
-      }
-    }
+  a.r0 = st.j0;
+  a.c0 = st.j1;
+#define BANET_X(f16)                                                                                            \
+  if (st.t0 == (f16 ? 1 : 0)) {                                                                                 \
+    hipLaunchKernelGGL(ba_syrk_rect_kernel<f16>, dim3(st.gx, st.gy), dim3(st.block), 0, s, a);                  \
+    return BANET_OK;                                                                                            \
   }
-  for (int r0 = 0; r0 < K; r0 += 128)        // off-diagonal 128 x 64 rectangles above the diagonal slices
-    for (int c0 = r0 + 128; c0 < K; c0 += 64) {
-      a.r0 = r0;
-      a.c0 = c0;
-      if (f16) hipLaunchKernelGGL(ba_syrk_rect_kernel<true>, dim3(Gs, B), dim3(kBlock), 0, s, a);
-      else hipLaunchKernelGGL(ba_syrk_rect_kernel<false>, dim3(Gs, B), dim3(kBlock), 0, s, a);
-    }
-  return hipGetLastError() == hipSuccess ? BANET_OK : BANET_ERR_LAUNCH;
+  BANET_SYRK_RECT_LIST(BANET_X)
+#undef BANET_X
+  return BANET_ERR_UNSUPPORTED;
 }
 
 }  // namespace banet

@@ -50,3 +50,153 @@ extern "C" const char* banet_test_dev_flags() {
 #undef X
   return s.c_str();
 }
+
+// ---- the SYRK step list and the role decision (tests/test_syrk_steps_cpu.py) -------------------------------------------------------
+#include <cstdio>
+#include <set>
+
+namespace {
+
+std::string fmt(const char* f, int a = 0, int b = 0, int c = 0, int d = 0) {
+  char buf[96];
+  snprintf(buf, sizeof buf, f, a, b, c, d);
+  return buf;
+}
+const char* tf(int v) { return v ? "true" : "false"; }
+
+// the kernel a step names, spelled as in the sources
+std::string step_kernel(const banet::SyrkStep& st) {
+  switch (st.kind) {
+    case banet::kSyrkStepZero: return "zero_iters_kernel";
+    case banet::kSyrkStepColmax: return "ba_colmax_kernel";
+    case banet::kSyrkStepRecmax: return "ba_recmax_kernel";
+    case banet::kSyrkStepSrsum: return "ba_srsum_kernel";
+    case banet::kSyrkStepLds: return fmt("ba_syrk_kernel<%d>", st.t0);
+    case banet::kSyrkStepMfma32: return fmt("ba_syrk_direct_kernel<%d, %d>", st.t0, st.t1);
+    case banet::kSyrkStepBf16x6: return fmt("ba_syrk_bf16x6_kernel<%d, %d, %d>", st.t0, st.t1, st.t2);
+    case banet::kSyrkStepSlice: return fmt("ba_syrk_slice_kernel<%d, ", st.t0) + tf(st.t1) + ", " + tf(st.t2) + ">";
+    case banet::kSyrkStepRect: return std::string("ba_syrk_rect_kernel<") + tf(st.t0) + ">";
+  }
+  return "?";
+}
+// "kernel job(..) grid(x, y) block n lds n[ attr]": job = words to zero / pass / (koff, p0) / (r0, c0), empty for the others
+std::string step_line(const banet::SyrkStep& st) {
+  std::string job = "job()";
+  if (st.kind == banet::kSyrkStepZero || st.kind == banet::kSyrkStepLds) job = fmt("job(%d)", st.j0);
+  if (st.kind == banet::kSyrkStepSlice || st.kind == banet::kSyrkStepRect) job = fmt("job(%d, %d)", st.j0, st.j1);
+  return step_kernel(st) + " " + job + fmt(" grid(%d, %d) block %d lds %d", st.gx, st.gy, st.block, st.lds) + (st.lds_attr ? " attr" : "");
+}
+
+struct LevelSteps {
+  int rc_plan, rc;
+  banet::SyrkRole role;
+  banet::SyrkSteps steps;
+};
+// role_mode 0: no role; 1: decided as for a bundle level whose damping comes from the lambda MLP.  stats: a SyrkStats value, or
+// kStatsSinglePass = what a single assembly pass of the level runs with
+constexpr int kStatsSinglePass = 100;
+LevelSteps level_steps(const int32_t* desc, int cus, int stats, int role_mode) {
+  banet_level_t lv = {};
+  lv.B = desc[0], lv.N = desc[1], lv.C = desc[2], lv.K = desc[3], lv.H = desc[4], lv.W = desc[5];
+  lv.dense = desc[6], lv.tgt_has_grad = desc[7], lv.pairs = desc[8], lv.policy = desc[9], lv.flags = desc[10];
+  lv.scale = 1.f;
+  LevelSteps r = {};
+  banet::AsmPlan p;
+  r.rc_plan = r.rc = banet::plan_assemble(&lv, cus, &p);
+  if (r.rc_plan != BANET_OK) return r;
+  r.role = banet::plan_syrk_role(p.s, role_mode != 0, banet::selection_batch(&lv), lv.N, lv.C, lv.flags, cus);
+  const banet::SyrkStats mode = stats == kStatsSinglePass ? banet::syrk_stats_of_single_pass(p.s) : (banet::SyrkStats)stats;
+  r.rc = banet::plan_syrk_steps(p.s, lv.B, lv.N, lv.K, banet::npairs(&lv), cus, mode, r.role, &r.steps);
+  return r;
+}
+
+}  // namespace
+
+// one line per level of `desc` (rows as banet_test_plan_sweep's): "rc=<plan_syrk_steps' code> role=<on> Gs=<rows launched>" and then
+// "; <step>" per launch, in order.  Returns the bytes `text` needs (with its terminator).
+extern "C" size_t banet_test_syrk_steps(const int32_t* desc, int n, int cus, int stats, int role_mode, char* text, size_t cap) {
+  std::string all;
+  for (int i = 0; i < n; ++i, desc += kDescInts) {
+    const LevelSteps r = level_steps(desc, cus, stats, role_mode);
+    all += fmt("rc=%d role=%d Gs=%d", r.rc, r.role.on, r.role.Gs);
+    for (int k = 0; k < r.steps.n; ++k) all += "; " + step_line(r.steps.step[k]);
+    all += "\n";
+  }
+  if (text && cap > all.size()) all.copy(text, all.size()), text[all.size()] = 0;
+  return all.size() + 1;
+}
+
+// the same over many levels without the text: out = (plan_assemble's code, plan_syrk_steps' code, steps) per level; returns the
+// distinct kernels the steps named, one per line
+extern "C" const char* banet_test_syrk_steps_sweep(const int32_t* desc, int n, int cus, int stats, int role_mode, int32_t* out) {
+  static std::string s;
+  std::set<std::string> seen;
+  for (int i = 0; i < n; ++i, desc += kDescInts) {
+    const LevelSteps r = level_steps(desc, cus, stats, role_mode);
+    *out++ = r.rc_plan, *out++ = r.rc, *out++ = r.steps.n;
+    for (int k = 0; k < r.steps.n; ++k) seen.insert(step_kernel(r.steps.step[k]));
+  }
+  s.clear();
+  for (const std::string& k : seen) s += k + "\n";
+  return s.c_str();
+}
+
+extern "C" int banet_test_syrk_max_steps() { return banet::kSyrkMaxSteps; }
+
+// every instantiation of the X-macro lists, one per line
+extern "C" const char* banet_test_syrk_instantiations() {
+  static std::string s;
+  s.clear();
+#define X(nb) s += fmt("ba_syrk_kernel<%d>\n", nb);
+  BANET_SYRK_LDS_LIST(X)
+#undef X
+  // (frames first: the list of frame counts is crossed with each of the three lists below)
+#define FRAMES(p) s += fmt(f_, p, a_, b_);
+#define X(kh)                                                 \
+  {                                                           \
+    const char* f_ = "ba_syrk_direct_kernel<%2$d, %1$d>\n";   \
+    const int a_ = kh, b_ = 0;                                \
+    BANET_SYRK_FRAMES_LIST(FRAMES)                            \
+  }
+  BANET_SYRK_MFMA32_LIST(X)
+#undef X
+#define X(kh, t)                                                    \
+  {                                                                 \
+    const char* f_ = "ba_syrk_bf16x6_kernel<%2$d, %1$d, %3$d>\n";   \
+    const int a_ = kh, b_ = t;                                      \
+    BANET_SYRK_FRAMES_LIST(FRAMES)                                  \
+  }
+  BANET_SYRK_BF16X6_LIST(X)
+#undef X
+#define X(dd, f16)                                                        \
+  {                                                                       \
+    const char* f_ = "ba_syrk_slice_kernel<%1$d, " #dd ", " #f16 ">\n";   \
+    const int a_ = 0, b_ = 0;                                             \
+    BANET_SYRK_FRAMES_LIST(FRAMES)                                        \
+  }
+  BANET_SYRK_SLICE_LIST(X)
+#undef X
+#undef FRAMES
+#define X(f16) s += "ba_syrk_rect_kernel<" #f16 ">\n";
+  BANET_SYRK_RECT_LIST(X)
+#undef X
+  return s.c_str();
+}
+
+// plan_syrk_role on hand-made plans: one row of `desc` = Gs, direct, bundle_mlp, Bsel, N, C, flags, cus; out = (on, Gs) per row
+extern "C" void banet_test_syrk_role(const int32_t* desc, int n, int32_t* out) {
+  for (int i = 0; i < n; ++i, desc += 8) {
+    banet::SyrkPlan pl = {};
+    pl.Gs = desc[0], pl.direct = desc[1];
+    const banet::SyrkRole r = banet::plan_syrk_role(pl, desc[2] != 0, desc[3], desc[4], desc[5], desc[6], desc[7]);
+    *out++ = r.on, *out++ = r.Gs;
+  }
+}
+
+// the statistics mode of iteration `it` of `max_iters` and of a single pass, for a plan with the given f16 / f16_standalone
+extern "C" void banet_test_syrk_stats(int f16, int f16_standalone, int it, int max_iters, int32_t* out) {
+  banet::SyrkPlan pl = {};
+  pl.f16 = f16, pl.f16_standalone = f16_standalone;
+  out[0] = banet::syrk_stats_of_iteration(pl, it, max_iters);
+  out[1] = banet::syrk_stats_of_single_pass(pl);
+}

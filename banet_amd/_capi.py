@@ -158,6 +158,12 @@ class BasisFitOut(ctypes.Structure):
     _fields_ = [("Wc", _FP), ("normal", _FP), ("rhs", _FP), ("stats", _FP), ("status", _FP)]
 
 
+class Prior(ctypes.Structure):
+    """mirror of banet_prior_t (banet_prior_apply_f32 and the *_prior_ LM entries: every pointer optional, reserved_ = 0)"""
+    _fields_ = [("Lambda", _FP), ("eta", _FP), ("obs_depth", _FP), ("obs_weight", _FP), ("scale", ctypes.c_float),
+                ("reserved_", ctypes.c_int32)]
+
+
 ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2  # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
 
 EXPORTS = {
@@ -209,6 +215,14 @@ EXPORTS = {
                                              ctypes.c_size_t, _FP]),
     "banet_lm_solve_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Schedule)]),
     "banet_lm_solve_f32": (ctypes.c_int, [ctypes.POINTER(Schedule), ctypes.POINTER(State), _FP]),
+    "banet_prior_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.POINTER(Prior)]),
+    "banet_prior_apply_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Prior)] + [_FP] * 3 + [_FP, ctypes.c_size_t, _FP]),
+    "banet_lm_level_prior_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.POINTER(Prior)]),
+    "banet_lm_level_prior_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float, ctypes.c_int,
+                                                ctypes.POINTER(LmParams), ctypes.POINTER(Prior), ctypes.POINTER(State), _FP,
+                                                ctypes.c_size_t, _FP]),
+    "banet_lm_solve_prior_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Schedule), ctypes.POINTER(Prior)]),
+    "banet_lm_solve_prior_f32": (ctypes.c_int, [ctypes.POINTER(Schedule), ctypes.POINTER(Prior), ctypes.POINTER(State), _FP]),
     "banet_sample_stats_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "banet_sample_stats_grad_det_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 5 + [_FP] * 5 + [_FP, ctypes.c_size_t, _FP]),
     "banet_spd_solve_f32": (ctypes.c_int, [_FP] * 3 + [ctypes.c_int] * 2 + [_FP]),

@@ -112,6 +112,7 @@ int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base
   }
   run->lv = lv;
   run->mlp = mlp;
+  run->prior = PriorRun{};   // (off: lm_level_prior_plan turns it on)
   run->max_iters = max_iters;
   run->lm = early_termination && lv->variant == BANET_LEGACY_LM;
   run->role = SyrkRole{0, pl.s.Gs};
@@ -126,6 +127,29 @@ int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base
                                lv->flags, num_cus());
     if (run->role.on) a.mlp_y = w.mlp_y;
   }
+  return BANET_OK;
+}
+
+size_t lm_level_prior_bytes(const banet_level_t* lv, const banet_prior_t* pr) {
+  AsmPlan apl;
+  if (plan_assemble(lv, num_cus(), &apl) != BANET_OK) return 0;
+  PriorPlan pl;
+  if (plan_prior_layout(lv, pr, carve_level(lv, apl, nullptr).total, &pl) != BANET_OK) return 0;
+  return pl.bytes;
+}
+
+int lm_level_prior_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, const banet_lm_params_t* params,
+                        const banet_prior_t* pr, const banet_state_t* st, void* ws, size_t ws_bytes, LevelRun* run) {
+  int rc = plan_detail::prior_struct_ok(pr);
+  if (rc != BANET_OK) return rc;
+  rc = lm_level_plan(lv, mlp, l2_base, max_iters, 0, params, st, ws, ws_bytes, run);
+  if (rc != BANET_OK) return rc;
+  PriorPlan pl;
+  rc = plan_prior(lv, pr, run->w.total, &pl);
+  if (rc != BANET_OK) return rc;
+  if (!pl.on) return BANET_OK;   // the empty prior: banet_lm_level_ex_f32's launches and workspace need
+  if (ws_bytes < pl.bytes) return BANET_ERR_WORKSPACE;
+  run->prior = make_prior_run(lv, pr, pl, ws);
   return BANET_OK;
 }
 
@@ -155,10 +179,20 @@ int lm_level_enqueue(const LevelRun& run, hipStream_t s) {
   } else {
     launch_zero_iters(st->iters, lv->B, s);
     if (a.queue) launch_zero_iters(a.queue, lv->B * a.nqueue, s);   // a kernel, not hipMemsetAsync: see prepare_gather
+    if (run.prior.pl.on && max_iters > 0) {   // Le, ee: constant over the level's iterations (prior.hip)
+      RangeScope r("prior_setup", lv->N);
+      rc = launch_prior_setup(lv, run.prior, s);
+      if (rc != BANET_OK) return rc;
+    }
     for (int it = 0; it < max_iters; ++it) {
       rc = launch_assemble(lv, pl, st->R, st->T, st->Wc, nullptr, 0, w.partials, w.AtA, w.Atb, w.absres, w.nvalid, s,
                            syrk_stats_of_iteration(pl.s, it, max_iters), a.queue == nullptr, &run.role, run.mlp, w.mlp_y);
       if (rc != BANET_OK) return rc;
+      if (run.prior.pl.on) {   // the depth block of AtA / Atb, before the damping
+        RangeScope r("prior", lv->N);
+        rc = launch_prior_add(run.prior, st->Wc, w.AtA, w.Atb, s);
+        if (rc != BANET_OK) return rc;
+      }
       {
         RangeScope r("solve", lv->N);
         rc = launch_solve(a, s);
@@ -436,6 +470,17 @@ int banet_lm_level_ex_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float
                           size_t ws_bytes, banet_stream_t stream) {
   LevelRun run;
   const int rc = lm_level_plan(lv, mlp, l2_base, max_iters, early_termination, params, st, ws, ws_bytes, &run);
+  if (rc != BANET_OK) return rc;
+  return lm_level_enqueue(run, static_cast<hipStream_t>(stream));
+}
+
+size_t banet_lm_level_prior_workspace_bytes(const banet_level_t* lv, const banet_prior_t* pr) { return lm_level_prior_bytes(lv, pr); }
+
+int banet_lm_level_prior_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters,
+                             const banet_lm_params_t* params, const banet_prior_t* pr, banet_state_t* st, void* ws,
+                             size_t workspace_bytes, banet_stream_t stream) {
+  LevelRun run;
+  const int rc = lm_level_prior_plan(lv, mlp, l2_base, max_iters, params, pr, st, ws, workspace_bytes, &run);
   if (rc != BANET_OK) return rc;
   return lm_level_enqueue(run, static_cast<hipStream_t>(stream));
 }

@@ -22,9 +22,7 @@
 
 namespace banet {
 
-constexpr int kFitThreads = 256;          // (a): 4 waves
-constexpr int kFitRowsMax = 64;           // partial rows per window at most
-constexpr int kFitRowPixels = 256;        // ... and never fewer pixels than this per row
+constexpr int kFitThreads = 256;          // (a): 4 waves  (kFitRowsMax / kFitRowPixels, the partial rows: prior_plan.hpp)
 constexpr int kFitSolveThreads = 1024;    // (c): 16 columns x 64 rows of threads over the trailing blocks
 constexpr int kFitCols = 16, kFitRowsT = kFitSolveThreads / kFitCols;
 constexpr size_t kFitLdsMax = 160 * 1024;
@@ -36,15 +34,12 @@ int plan_basis_fit(const banet_level_t* lv, FitPlan* pl) {
   if (lv->K < 1 || lv->K > kFitKMax || lv->N < 1) return BANET_ERR_UNSUPPORTED;
   const int K = lv->K, N = lv->N;
   pl->K = K;
-  pl->NR = (K + 31) / 32;
-  pl->NP = pl->NR * (pl->NR + 1) / 2;
-  int rows = (N + kFitRowPixels - 1) / kFitRowPixels;
-  if (rows > kFitRowsMax) rows = kFitRowsMax;
-  int chunk = (N + rows - 1) / rows;
-  chunk = (chunk + 1) / 2 * 2;                       // whole two-pixel steps
-  pl->chunk = chunk;
-  pl->rows = (N + chunk - 1) / chunk;
-  pl->pstride = pl->NP * 1024 + pl->NR * 32 + 32;    // floats per partial row: the blocks, g, (sum w, sum w r^2) + padding
+  const FitRows fr = fit_rows(N, K);                 // (prior_plan.hpp: the prior's observation half runs the same rows)
+  pl->NR = fr.NR;
+  pl->NP = fr.NP;
+  pl->chunk = fr.chunk;
+  pl->rows = fr.rows;
+  pl->pstride = fr.pstride;
   const size_t mat = (size_t)K * (K + 1) / 2 * sizeof(double), vecs = 2 * (size_t)K * sizeof(double);
   pl->big = mat + vecs > kFitLdsMax;
   pl->lds = pl->big ? vecs : mat + vecs;
@@ -337,21 +332,22 @@ static void launch_fit_gram(const FitArgs& a, int B, hipStream_t s) {
   hipLaunchKernelGGL((fit_gram_kernel<NR, S>), dim3(gx, B), dim3(kFitThreads), 0, s, a);
 }
 
-int launch_basis_fit(const banet_level_t* lv, const FitPlan& pl, const float* target, const float* weight, const float* damping,
-                     const banet_basis_fit_out_t* out, void* ws, hipStream_t s) {
-  char* w = static_cast<char*>(ws);
+// (a) + (b): the Gram pass over the rows `fr` and its fold.  G / g go to Gws / gws and to normal / rhs / stats where given.  The
+// first two launches of banet_basis_fit_f32, and the observation half of a prior (prior.hip), whose G / g are therefore its bits.
+int launch_fit_gram_fold(const banet_level_t* lv, const FitRows& fr, const float* target, const float* weight, float* part, float* Gws,
+                         float* gws, float* normal, float* rhs, float* stats, hipStream_t s) {
   FitArgs a;
   a.N = lv->N;
-  a.K = pl.K;
-  a.chunk = pl.chunk;
-  a.rows = pl.rows;
-  a.pstride = pl.pstride;
+  a.K = lv->K;
+  a.chunk = fr.chunk;
+  a.rows = fr.rows;
+  a.pstride = fr.pstride;
   a.depth = lv->depth;
   a.basis = lv->basis;
   a.target = target;
   a.weight = weight;
-  a.part = reinterpret_cast<float*>(w + pl.off_part);
-  switch (pl.NR) {
+  a.part = part;
+  switch (fr.NR) {
     case 1: launch_fit_gram<1, 1>(a, lv->B, s); break;
     case 2: launch_fit_gram<2, 1>(a, lv->B, s); break;
     case 3: launch_fit_gram<3, 1>(a, lv->B, s); break;
@@ -365,25 +361,37 @@ int launch_basis_fit(const banet_level_t* lv, const FitPlan& pl, const float* ta
   if (hipGetLastError() != hipSuccess) return BANET_ERR_LAUNCH;
 
   FoldArgs f;
-  f.K = pl.K;
-  f.NR = pl.NR;
-  f.NP = pl.NP;
-  f.rows = pl.rows;
-  f.pstride = pl.pstride;
-  f.part = a.part;
-  f.Gws = reinterpret_cast<float*>(w + pl.off_G);
-  f.gws = reinterpret_cast<float*>(w + pl.off_g);
-  f.normal = out->normal;
-  f.rhs = out->rhs;
-  f.stats = out->stats;
-  const int total = pl.NP * 1024 + pl.NR * 32 + 2;
+  f.K = lv->K;
+  f.NR = fr.NR;
+  f.NP = fr.NP;
+  f.rows = fr.rows;
+  f.pstride = fr.pstride;
+  f.part = part;
+  f.Gws = Gws;
+  f.gws = gws;
+  f.normal = normal;
+  f.rhs = rhs;
+  f.stats = stats;
+  const int total = fr.NP * 1024 + fr.NR * 32 + 2;
   hipLaunchKernelGGL(fit_fold_kernel, dim3((total + 255) / 256, lv->B), dim3(256), 0, s, f);
   if (hipGetLastError() != hipSuccess) return BANET_ERR_LAUNCH;
+  return BANET_OK;
+}
+
+int launch_basis_fit(const banet_level_t* lv, const FitPlan& pl, const float* target, const float* weight, const float* damping,
+                     const banet_basis_fit_out_t* out, void* ws, hipStream_t s) {
+  char* w = static_cast<char*>(ws);
+  float* Gws = reinterpret_cast<float*>(w + pl.off_G);
+  float* gws = reinterpret_cast<float*>(w + pl.off_g);
+  const FitRows fr = {pl.NR, pl.NP, pl.chunk, pl.rows, pl.pstride};
+  const int rc = launch_fit_gram_fold(lv, fr, target, weight, reinterpret_cast<float*>(w + pl.off_part), Gws, gws, out->normal, out->rhs,
+                                      out->stats, s);
+  if (rc != BANET_OK) return rc;
 
   FitSolveArgs q;
   q.K = pl.K;
-  q.G = f.Gws;
-  q.g = f.gws;
+  q.G = Gws;
+  q.g = gws;
   q.damping = damping;
   q.Wc = out->Wc;
   q.status = out->status;

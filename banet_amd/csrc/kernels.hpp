@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "grid_plan.hpp"   // the grid resampler's geometry (host-only like plan.hpp)
+#include "prior_plan.hpp"  // the prior term's regions and the Gram pass's partial rows (host-only like plan.hpp)
 
 namespace banet {
 
@@ -124,6 +125,26 @@ struct FitPlan {    // the workspace of one call; host memory only
 int plan_basis_fit(const banet_level_t* lv, FitPlan* pl);
 int launch_basis_fit(const banet_level_t* lv, const FitPlan& pl, const float* target, const float* weight, const float* damping,
                      const banet_basis_fit_out_t* out, void* ws, hipStream_t s);
+// its first two launches (Gram pass over the rows `fr` = fit_rows(N, K), fold): G / g to Gws / gws, and to normal / rhs / stats where given
+int launch_fit_gram_fold(const banet_level_t* lv, const FitRows& fr, const float* target, const float* weight, float* part, float* Gws,
+                         float* gws, float* normal, float* rhs, float* stats, hipStream_t s);
+
+// ---- prior.hip: depth observations and coefficient priors between assembly and solve (banet_prior_apply_f32, the *_prior_ LM entries;
+//      plan: prior_plan.hpp) ----
+struct PriorRun {   // a planned prior next to its pointers; host memory only.  pl.on == 0: nothing is launched
+  PriorPlan pl;
+  banet_prior_t pr;
+  int B;
+  float* Le;        // [B][K][K] inside the workspace
+  float* ee;        // [B][K]
+  float* part;      // pl.obs: the Gram pass's partial rows, G and g (nullptr otherwise)
+  float* G;
+  float* g;
+};
+// pl: plan_prior's for (lv, pr), its offsets relative to `ws`
+PriorRun make_prior_run(const banet_level_t* lv, const banet_prior_t* pr, const PriorPlan& pl, void* ws);
+int launch_prior_setup(const banet_level_t* lv, const PriorRun& run, hipStream_t s);   // once per level: Le, ee
+int launch_prior_add(const PriorRun& run, const float* Wc, float* AtA, float* Atb, hipStream_t s);   // every iteration
 
 // ---- prep.hip --------------------------------------------------------------------------
 int launch_resample(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,
@@ -256,11 +277,17 @@ struct LevelRun {   // what lm_level_plan decided; host memory only
   int max_iters;
   bool lm;     // device-side loop control (BANET_LEGACY_LM with early termination)
   SyrkRole role;   // role.on: the lambda MLP runs as a role workgroup of the SYRK launch, on role.Gs partial rows per window
+  PriorRun prior;  // prior.pl.on: one launch_prior_add between assembly and solve of every iteration (lm_level_prior_plan; off otherwise)
 };
 // every check of banet_lm_level_ex_f32, in its order and with its return codes; launches nothing
 int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, int early_termination,
                   const banet_lm_params_t* params, const banet_state_t* st, void* ws, size_t ws_bytes, LevelRun* run);
 int lm_level_enqueue(const LevelRun& run, hipStream_t s);
+// the same for banet_lm_level_prior_f32 (early_termination = 0): the level's checks, then the prior's; the prior's regions lie behind
+// the level's carve
+int lm_level_prior_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, const banet_lm_params_t* params,
+                        const banet_prior_t* pr, const banet_state_t* st, void* ws, size_t ws_bytes, LevelRun* run);
+size_t lm_level_prior_bytes(const banet_level_t* lv, const banet_prior_t* pr);   // the query: 0 = unsupported / invalid
 
 // ---- schedule.hip --------------------------------------------------------------------------
 struct TraceRow {   // one level's row of banet_solve_trace_t (nullptr: not recorded) next to the state it is copied from

@@ -18,6 +18,34 @@ DenseMarginals = collections.namedtuple("DenseMarginals", "pose_cov depth_var wf
 DepthTransfer = collections.namedtuple("DepthTransfer", "Wc depth_map index covered status")
 
 
+class DensePrior:
+    """What DenseBA.solve(prior=...) additionally minimises on every level l (ops.Prior, include/banet_hip.h (5d)):
+        level_scale[l] (1/2 Wc^T Lambda Wc - eta^T Wc + 1/2 sum_n w_n (obs_n - depth_n - b_n . Wc)^2)
+      coef        (Lambda [B,K,K], eta [B,K] or None), the same on every level (the coefficients are), or None
+      depth_obs   one (obs, weight) pair per level, each [B,H_l,W_l] (weight None: 1), or None entries / None
+      level_scale one factor per level (default 1)."""
+
+    def __init__(self, coef=None, depth_obs=None, level_scale=None):
+        self.coef = coef
+        self.depth_obs = list(depth_obs) if depth_obs is not None else None
+        self.level_scale = list(level_scale) if level_scale is not None else None
+
+    def level_priors(self, problems):
+        """-> one ops.Prior per level"""
+        n = len(problems)
+        if (self.depth_obs is not None and len(self.depth_obs) < n) or (self.level_scale is not None and len(self.level_scale) < n):
+            raise ops.capi.BanetError("DensePrior: depth_obs / level_scale need one entry per level (%d)" % n)
+        Lambda, eta = self.coef if self.coef is not None else (None, None)
+        out = []
+        for l, p in enumerate(problems):
+            obs = self.depth_obs[l] if self.depth_obs is not None else None
+            o, w = obs if obs is not None else (None, None)
+            o = o.reshape(p.B, p.N) if o is not None else None
+            w = w.reshape(p.B, p.N) if w is not None else None
+            out.append(ops.Prior(Lambda, eta, o, w, scale=1.0 if self.level_scale is None else float(self.level_scale[l])))
+        return out
+
+
 class DenseLevel:
     def __init__(self, scale, src, tgt, depth, basis=None):
         """tgt [B,H,W,C] (2-frame) or [B,pairs,H,W,C] (multi-frame window: `pairs` target frames that
@@ -116,18 +144,30 @@ class DenseBA:
     c_schedule = True
 
     def solve(self, iters_per_level, state=None, early_termination=False, params=None, snapshots=None, level_events=None,
-              depth_outputs=None):
+              depth_outputs=None, prior=None):
         """Enqueue the full schedule; returns the state (R,T,Wc updated in place) and the list
         of per-level iteration-count tensors.  params: ops.lm_params(...) (legacy/ba.py:5-9) or None for the
         reference's defaults.  snapshots: a list that receives, per level, a dict of (R, T, W, delta, lam)
         after that level (device tensors, no host sync).  level_events: a list that receives one (start, end) pair of
         torch.cuda.Event per level, recorded on the current stream (per-level times without a host sync).  depth_outputs: a list
         that receives, per level, the depth map depth_l + basis_l . Wc after that level, shaped like the level's depth
-        (bundlenet.py:397 output_depths; `bundle` only)."""
+        (bundlenet.py:397 output_depths; `bundle` only).  prior: a DensePrior -- depth observations and / or a prior on the
+        coefficients, added between assembly and solve of every iteration (`bundle` only, no early termination; the same bits on
+        the one-call path and on the per-level path); None = the call path without one."""
         st = state if state is not None else self.new_state()
         if depth_outputs is not None and self.variant != "bundle":
             raise ops.capi.BanetError("DenseBA.solve: depth_outputs need the `bundle` variant (a depth basis)")
         n = min(len(self.problems), len(iters_per_level))
+        priors = None
+        if prior is not None:
+            if self.variant != "bundle" or early_termination:
+                raise ops.capi.BanetError("DenseBA.solve: a prior needs the `bundle` variant and excludes early termination")
+            priors = prior.level_priors(self.problems[:n])
+            need = [ops.lm_level_workspace_bytes(p, q) for p, q in zip(self.problems[:n], priors)]
+            if min(need) == 0:
+                raise ops.capi.BanetError("DenseBA.solve: the prior does not fit the levels")
+            if self.ws.numel() < max(need):
+                self.ws = ops.capi.workspace(max(need), self.intr.device)
         if self.c_schedule and level_events is None and not self.split_coarse and 1 <= n <= 16:
             # one call: counts / snapshots are views of the trace rows (allocated per call), nothing is cloned per level
             depth = None
@@ -135,7 +175,7 @@ class DenseBA:
                 depth = [torch.empty((p.B, p.N), dtype=torch.float32, device=p.device) for p in self.problems[:n]]
             trace = ops.SolveTrace(n, st, fields=None if snapshots is not None else ("iters",), depth=depth)
             ops.lm_solve(self.problems[:n], self.mlps[:n], self.l2_base, list(iters_per_level[:n]), early_termination, st,
-                         ws=self.ws, params=params, trace=trace)
+                         ws=self.ws, params=params, trace=trace, priors=priors)
             if snapshots is not None:
                 snapshots.extend(dict(R=trace.R[l], T=trace.T[l], W=None if trace.Wc is None else trace.Wc[l],
                                       delta=trace.delta[l], lam=trace.lambda_out[l]) for l in range(n))
@@ -148,7 +188,7 @@ class DenseBA:
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record()
             li = len(counts)
-            if self.split_coarse and self.B >= 16 and prob.N <= 1200 and li < len(self.levels):
+            if self.split_coarse and priors is None and self.B >= 16 and prob.N <= 1200 and li < len(self.levels):
                 # two half batches, the second on a side stream; joined before the next level (the state tensors are shared)
                 dev = self.intr.device
                 cur = torch.cuda.current_stream(dev)
@@ -161,7 +201,8 @@ class DenseBA:
                     ops.lm_level(p1, mlp, self.l2_base, its, early_termination, s1, ws=w1, params=params)
                 cur.wait_stream(self._side)
             else:
-                ops.lm_level(prob, mlp, self.l2_base, its, early_termination, st, ws=self.ws, params=params)
+                ops.lm_level(prob, mlp, self.l2_base, its, early_termination, st, ws=self.ws, params=params,
+                             prior=priors[li] if (priors is not None and li < len(priors)) else None)
             if level_events is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
@@ -308,6 +349,36 @@ class DenseBA:
             fit = ops.basis_fit(new_depth.detach().reshape(B, H * W), new_basis.detach().reshape(B, H * W, -1), depth_map.reshape(B, H * W),
                                 weight=weight.reshape(B, H * W), damping=damping)
             return DepthTransfer(fit.Wc, depth_map, index, hit.reshape(B, -1).sum(dim=1), fit.status)
+
+    def transfer_prior(self, level_index, state, new_depth, new_basis, frame=0, depth_var=None, damping=1e-3):
+        """transfer_depth, and what the transferred depth says about the new key frame's coefficients as a prior for the next window's
+        solve: the same three steps (the fit's optional outputs do not change its bits) ->
+        (DepthTransfer, DensePrior(coef=(fit.normal, fit.rhs), level_scale)) with level_scale[l] = N_l / N_level_index over THIS
+        solver's levels, so that the term keeps its weight next to a feature term that grows with the pixel count.  The next window's
+        DenseBA (same pyramid, the new key frame's depth and basis) takes it as solve(prior=...), from Wc = the transfer's."""
+        p = self.problems[level_index]
+        B, H, W = p.B, int(p.c.H), int(p.c.W)
+        if not 0 <= int(frame) < p.pairs:
+            raise ops.capi.BanetError("DenseBA.transfer_prior: frame %d of a window with %d target frames" % (frame, p.pairs))
+        if not (new_depth.is_cuda and new_basis.is_cuda) or (depth_var is not None and not depth_var.is_cuda):
+            raise ops.capi.BanetError("banet_amd runs on the GPU only")
+        if new_depth.numel() != B * H * W or new_basis.dim() != 4 or new_basis.numel() != B * H * W * new_basis.shape[-1]:
+            raise ops.capi.BanetError("DenseBA.transfer_prior: expected new_depth [B,H,W] and new_basis [B,H,W,K'] at the level's %d x %d" % (H, W))
+        with torch.no_grad():
+            rep = ops.depth_reproject(p, state.R, state.T, state.Wc if self.K > 0 else None)
+            depth_map, index = rep.depth[:, frame].contiguous(), rep.index[:, frame].contiguous()
+            hit = index >= 0
+            weight = hit.to(torch.float32)
+            if depth_var is not None:
+                if depth_var.numel() != B * H * W:
+                    raise ops.capi.BanetError("DenseBA.transfer_prior: depth_var must be [B,H,W]")
+                var = torch.gather(depth_var.detach().reshape(B, H * W).float(), 1, index.reshape(B, H * W).clamp(min=0).long())
+                weight = weight / (var.reshape(B, H, W) + self.transfer_eps)
+            fit = ops.basis_fit(new_depth.detach().reshape(B, H * W), new_basis.detach().reshape(B, H * W, -1), depth_map.reshape(B, H * W),
+                                weight=weight.reshape(B, H * W), damping=damping, want=("Wc", "normal", "rhs"))
+            scales = [q.N / float(p.N) for q in self.problems]
+            return (DepthTransfer(fit.Wc, depth_map, index, hit.reshape(B, -1).sum(dim=1), fit.status),
+                    DensePrior(coef=(fit.normal, fit.rhs), level_scale=scales))
 
     def cost_trace(self, snapshots, state0=None):
         """Did each level reduce the cost?  snapshots: what solve(snapshots=...) filled; state0: the state that solve started from

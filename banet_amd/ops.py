@@ -726,12 +726,75 @@ def ba_solve_update(level, mlp, l2_base, AtA, Atb, absres, nvalid, state, ws=Non
     return ws
 
 
-def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, params=None):
+class Prior:
+    """banet_prior_t plus the tensors it points at: what a level's solve additionally minimises, per window,
+        scale (1/2 Wc^T Lambda Wc - eta^T Wc + 1/2 sum_n w_n (obs_n - depth_n - b_n . Wc)^2)
+    Lambda [B,K,K] symmetric with eta [B,K] (None: 0) -- a Gaussian prior on the coefficients in information form, e.g.
+    basis_fit(...).normal / .rhs -- and / or obs_depth [B,N] (any shape with B leading) with obs_weight like it (None: 1), summed
+    over the points with a finite weight > 0 and a finite observation.  Each half may be None; a prior without tensors, or with
+    scale = 0, is the empty prior (the solve without it, bit for bit).  eta needs Lambda and obs_weight needs obs_depth."""
+
+    def __init__(self, Lambda=None, eta=None, obs_depth=None, obs_weight=None, scale=1.0):
+        keep = [capi.f32c(x) if x is not None else None for x in (Lambda, eta, obs_depth, obs_weight)]
+        self.Lambda, self.eta, self.obs_depth, self.obs_weight = keep
+        self.scale = float(scale)
+        self.c = capi.Prior()
+        for name, t in zip(("Lambda", "eta", "obs_depth", "obs_weight"), keep):
+            setattr(self.c, name, None if t is None else capi.ptr(t).value)   # (CPU tensors: BanetError)
+        self.c.scale = self.scale
+
+    def check(self, B, N, K):
+        for name, t, n in (("Lambda", self.Lambda, B * K * K), ("eta", self.eta, B * K), ("obs_depth", self.obs_depth, B * N),
+                           ("obs_weight", self.obs_weight, B * N)):
+            if t is not None and t.numel() != n:
+                raise capi.BanetError("Prior: %s holds %d values, the level (B = %d, N = %d, K = %d) needs %d" % (name, t.numel(), B, N, K, n))
+
+
+def prior_workspace_bytes(level, prior):
+    """banet_prior_workspace_bytes (0: the empty prior, or a level the term does not exist on)"""
+    return capi.lib().banet_prior_workspace_bytes(ctypes.byref(level.c), ctypes.byref(prior.c) if prior is not None else None)
+
+
+def prior_apply(level, prior, Wc, AtA, Atb, ws=None):
+    """banet_prior_apply_f32: one iteration's step of a Prior between ba_assemble and ba_solve_update, IN PLACE on AtA [B,P,P] and
+    Atb [B,P] at the coefficients Wc [B,K]: the depth block gets Le = fl(scale fl(G + Lambda)), Atb's depth rows
+    fl(scale fl(g + eta)) - Le Wc.  level: a LevelProblem (B, N, K, pairs, variant, depth and basis are read).  The empty prior
+    launches nothing.  -> the workspace used (None for the empty prior)."""
+    L = capi.lib()
+    lv = level.c
+    if prior is not None:
+        prior.check(int(lv.B), int(lv.N), int(lv.K))
+    pw, pa, pb = capi.ptr(Wc), capi.ptr(AtA), capi.ptr(Atb)
+    pc = ctypes.byref(prior.c) if prior is not None else None
+    nb = int(L.banet_prior_workspace_bytes(ctypes.byref(lv), pc))
+    if nb and (ws is None or ws.numel() < nb):
+        ws = capi.workspace(nb, AtA.device)
+    capi.check(L.banet_prior_apply_f32(ctypes.byref(lv), pc, pw, pa, pb, ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                       ws.numel() if ws is not None else 0, capi.stream()))
+    return ws
+
+
+def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, params=None, prior=None):
     """banet_lm_level_ex_f32: the whole LM loop of one pyramid level, enqueued without host sync.
-    params: an `lm_params(...)` value (None = the reference's defaults, legacy/ba.py:5-9)."""
+    params: an `lm_params(...)` value (None = the reference's defaults, legacy/ba.py:5-9).
+    prior: a `Prior` (banet_lm_level_prior_f32: its term is added between assembly and solve of every iteration; `bundle` levels,
+    no early termination); None = the call path without one."""
     L = capi.lib()
     if mlp is not None:
         mlp.check(level.C)
+    if prior is not None:
+        if early_termination:
+            raise capi.BanetError("lm_level: a prior excludes early termination")
+        prior.check(level.B, level.N, level.K)
+        nb = L.banet_lm_level_prior_workspace_bytes(ctypes.byref(level.c), ctypes.byref(prior.c))
+        if nb == 0:
+            raise capi.BanetError("lm_level: unsupported level shape, or a prior on a level without a depth basis")
+        if ws is None or ws.numel() < nb:
+            ws = capi.workspace(nb, level.device)
+        capi.check(L.banet_lm_level_prior_f32(ctypes.byref(level.c), ctypes.byref(mlp.c) if mlp is not None else None, float(l2_base),
+                                              int(max_iters), ctypes.byref(params) if params is not None else None, ctypes.byref(prior.c),
+                                              ctypes.byref(state.c), ctypes.c_void_p(ws.data_ptr()), ws.numel(), capi.stream()))
+        return ws
     nb = L.banet_lm_level_workspace_bytes(ctypes.byref(level.c))
     if nb == 0:
         raise capi.BanetError("lm_level: unsupported level shape")
@@ -744,7 +807,9 @@ def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, 
     return ws
 
 
-def lm_level_workspace_bytes(level):
+def lm_level_workspace_bytes(level, prior=None):
+    if prior is not None:
+        return capi.lib().banet_lm_level_prior_workspace_bytes(ctypes.byref(level.c), ctypes.byref(prior.c))
     return capi.lib().banet_lm_level_workspace_bytes(ctypes.byref(level.c))
 
 
@@ -809,12 +874,34 @@ def lm_solve_workspace_bytes(levels):
     return capi.lib().banet_lm_solve_workspace_bytes(ctypes.byref(s))
 
 
-def lm_solve(levels, mlps, l2_base, iters, early_termination, state, ws=None, params=None, trace=None):
+def lm_solve(levels, mlps, l2_base, iters, early_termination, state, ws=None, params=None, trace=None, priors=None):
     """banet_lm_solve_f32: every level of a coarse -> fine schedule in ONE call -- the sequence of lm_level calls, bit for bit,
     with the state after each level recorded in `trace` (a SolveTrace, or None).  levels / mlps / iters: one LevelProblem,
-    MlpWeights (or None) and iteration count per level.  All levels are validated before anything is enqueued."""
+    MlpWeights (or None) and iteration count per level.  All levels are validated before anything is enqueued.
+    priors: one `Prior` or None per level (banet_lm_solve_prior_f32; no early termination); None = the call path without."""
     L = capi.lib()
     s, keep = _schedule(levels, mlps, l2_base, iters, early_termination, params, trace)
+    if priors is not None:
+        n = len(levels)
+        if len(priors) != n:
+            raise capi.BanetError("lm_solve: %d priors for %d levels" % (len(priors), n))
+        if early_termination:
+            raise capi.BanetError("lm_solve: priors exclude early termination")
+        pr = (capi.Prior * n)()                            # (a zeroed entry is the empty prior)
+        for i, p in enumerate(priors):
+            if p is not None:
+                p.check(levels[i].B, levels[i].N, levels[i].K)
+                pr[i] = p.c
+        nb = L.banet_lm_solve_prior_workspace_bytes(ctypes.byref(s), pr)
+        if nb == 0:
+            raise capi.BanetError("lm_solve: unsupported level shape, levels that disagree in B / K / pairs / variant / policy, or a "
+                                  "prior on a level without a depth basis")
+        if ws is None or ws.numel() < nb:
+            ws = capi.workspace(nb, levels[0].device)
+        s.workspace, s.workspace_bytes = ws.data_ptr(), ws.numel()
+        capi.check(L.banet_lm_solve_prior_f32(ctypes.byref(s), pr, ctypes.byref(state.c), capi.stream()))
+        del keep
+        return ws
     nb = L.banet_lm_solve_workspace_bytes(ctypes.byref(s))
     if nb == 0:
         raise capi.BanetError("lm_solve: unsupported level shape, or levels that disagree in B / K / pairs / variant / policy")

@@ -536,6 +536,59 @@ typedef struct banet_schedule {
 size_t banet_lm_solve_workspace_bytes(const banet_schedule_t* s); /* reads levels / n_levels only */
 int banet_lm_solve_f32(const banet_schedule_t* s, banet_state_t* st, banet_stream_t stream);
 
+/* (5d) depth observations and coefficient priors inside the LM loop.  BANET_BUNDLE levels with K >= 1, dense or sparse, any pairs.
+ *     Per window the solve additionally minimises
+ *         scale (1/2 Wc^T Lambda Wc - eta^T Wc + 1/2 sum_n w_n (obs_n - depth_n - b_n . Wc)^2)
+ *     -- a Gaussian prior on the coefficients in information form (what banet_basis_fit_f32 returns as normal / rhs for the
+ *     previous window's transferred depth) and / or a depth observation per point (RGB-D, sparse LiDAR; w = obs_weight, NULL: 1),
+ *     the sum over the points banet_basis_fit_f32 counts: a finite w_n > 0 and a finite obs_n.  With G, g that fit's normal and rhs
+ *     for target = obs:
+ *         Le = fl(scale fl(G + Lambda))      ee = fl(scale fl(g + eta))      (a half that is not given is left out, not added as 0)
+ *         AtA[m+i, m+j] += Le[i,j]           Atb[m+i] += ee[i] - sum_j Le[i,j] Wc[j]          m = 6 max(pairs, 1), row stride P
+ *     between (3) and (4) of every iteration: before the damping, which therefore sees the prior on the diagonal.  lambda is still
+ *     predicted from the feature residuals alone (absres / nvalid).  D = depth + b . Wc is linear in Wc, so G and g are constant
+ *     over a level's iterations: Le and ee are formed once per level (the Gram pass and fold of banet_basis_fit_f32 -- G, g bit-equal
+ *     to its normal / rhs -- and one combine launch), and every iteration costs one more launch, ba_prior_add_kernel, one wave per
+ *     row of Le, no atomics, every output element written by exactly one lane.  Every summation order depends on N and K only: a
+ *     window's bits are the same alone and in any batch.
+ *     The EMPTY prior: pr == NULL, all four pointers NULL, or scale == 0.  banet_prior_apply_f32 then launches nothing;
+ *     banet_lm_level_prior_f32 is then exactly banet_lm_level_ex_f32 with early_termination = 0 (same launches, same bits, same
+ *     workspace need) and banet_lm_solve_prior_f32 exactly banet_lm_solve_f32.
+ *     BANET_ERR_INVALID_ARG, decided before any launch: eta without Lambda, obs_weight without obs_depth, a scale that is negative
+ *     or not finite, reserved_ != 0 (whatever the scale); NULL Wc / AtA / Atb (banet_prior_apply_f32); everything
+ *     banet_lm_level_ex_f32 / banet_lm_solve_f32 refuse, with their codes; s->early_termination != 0.  A prior that is not empty on
+ *     a variant other than BANET_BUNDLE or with K == 0 (K > 256, N < 1): BANET_ERR_UNSUPPORTED, and a query of 0.
+ *     Workspace: the queries read which pointers of pr are NULL and the level's shape, nothing else (not the scale);
+ *     banet_lm_level_prior_workspace_bytes = banet_lm_level_workspace_bytes plus the prior's regions behind it,
+ *     banet_lm_solve_prior_workspace_bytes the maximum over the levels (priors == NULL: no level has one).  NULL, misaligned or too
+ *     small: BANET_ERR_WORKSPACE.  banet_prior_apply_f32 is one iteration's step on the caller's AtA / Atb, in place (the once-per-
+ *     level launches included); it reads lv->B, N, K, pairs, variant, depth and basis and nothing else of the level.
+ *     banet_lm_solve_prior_f32: priors[l] belongs to levels[l]; all or nothing like banet_lm_solve_f32 -- a bad prior on the last
+ *     level enqueues nothing; bit-identical to the sequence of banet_lm_level_prior_f32 calls plus the trace copies.
+ *     Enqueue only: no allocation, no synchronisation, no global state, one stream, capturable.  BANET_VERSION is unchanged by this
+ *     addition: detect the entries by their symbols.                                                                           */
+typedef struct banet_prior {
+  const float* Lambda;      /* [B,K,K] symmetric, or NULL */
+  const float* eta;         /* [B,K], or NULL = 0; only with Lambda */
+  const float* obs_depth;   /* [B,N], or NULL */
+  const float* obs_weight;  /* [B,N], or NULL = 1; only with obs_depth */
+  float scale;              /* finite, >= 0 */
+  int32_t reserved_;        /* 0 */
+} banet_prior_t;
+
+size_t banet_prior_workspace_bytes(const banet_level_t* lv, const banet_prior_t* pr);
+int banet_prior_apply_f32(const banet_level_t* lv, const banet_prior_t* pr, const float* Wc, float* AtA, float* Atb, void* ws,
+                          size_t workspace_bytes, banet_stream_t stream);
+
+size_t banet_lm_level_prior_workspace_bytes(const banet_level_t* lv, const banet_prior_t* pr);
+int banet_lm_level_prior_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters,
+                             const banet_lm_params_t* params, const banet_prior_t* pr, banet_state_t* st, void* ws,
+                             size_t workspace_bytes, banet_stream_t stream);
+
+size_t banet_lm_solve_prior_workspace_bytes(const banet_schedule_t* s, const banet_prior_t* priors);
+int banet_lm_solve_prior_f32(const banet_schedule_t* s, const banet_prior_t* priors /* n_levels entries, or NULL */,
+                             banet_state_t* st, banet_stream_t stream);
+
 /* (6) per-level preparation -- the step immediately before the LM loop.
  *   banet_resample_f32   data [B,H,W,C], warp [B,N,2] (x,y) -> out [B,N,C]
  *       mode BANET_RESAMPLE_ZERO_PAD : tf.contrib.resampler.resampler as called at

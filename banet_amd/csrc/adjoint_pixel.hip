@@ -24,7 +24,7 @@ __device__ __forceinline__ float wsum(float v) {
 // SP (round 5): SPARSE points in the reference's own layout -- what bundlenet.py:332-399 trains on: conv1 [B,N,C] sampled at N points,
 // rays p [B,3,N] and per-point level intrinsics supplied (bundlenet.py:115-119), the target map precomputed as [f|gx|gy]
 // [B,H,W,3C] (bundlenet.py:92-100) and sampled with plain bilinear taps, clamped one by one like the forward's generic kernel
-// (gather.hip, GRAD = true).  Same per-pixel algebra; dmap3 is then the gradient of that 3C map itself.
+// (gather_generic.hip, GRAD = true).  Same per-pixel algebra; dmap3 is then the gradient of that 3C map itself.
 template <int CJ, int KJ, bool SP = false>   // C <= 64 CJ, K <= 64 KJ (K > 128: 2 waves per SIMD -- the per-coefficient state would spill at 3)
 __global__ __launch_bounds__(kBlock, (KJ >= 3 ? 2 : 3)) void adj_pixel_kernel(const AdjArgs a) {
   const banet_level_t& lv = a.lv;

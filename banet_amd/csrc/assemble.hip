@@ -156,18 +156,20 @@ int launch_assemble(const banet_level_t* lv, const AsmPlan& pl, const float* R, 
   float* gpart = reinterpret_cast<float*>(base);
   float* rec = lv->K > 0 ? reinterpret_cast<float*>(base + pl.off_rec) : nullptr;
   float* spart = lv->K > 0 ? reinterpret_cast<float*>(base + pl.off_spart) : nullptr;
-  int rc;
-  if (reset_queue) prepare_gather(lv, pl.g, gpart, s);
+  GatherSteps gsteps;
+  int rc = plan_gather_steps(lv, pl.g, reset_queue, &gsteps);   // a shape without a compiled gather kernel is refused before anything is enqueued
+  if (rc != BANET_OK) return rc;
+  prepare_gather(gsteps, pl.g, gpart, s);
   {
     RangeScope r("gather", lv->N);
     Timed t(s, lv->N);
-    rc = launch_gather(lv, pl.g, R, T, Wc, active, active_stride, rec, gpart, s, mask_out);
+    rc = launch_gather(gsteps, lv, pl.g, R, T, Wc, active, active_stride, rec, gpart, s, mask_out);
   }
   if (rc != BANET_OK) return rc;
   const float* gred;
   {
     RangeScope r("fold", lv->N);
-    gred = finish_gather(lv, pl.g, active, active_stride, gpart, s);
+    gred = finish_gather(gsteps, lv, pl.g, active, active_stride, gpart, s);
   }
   const SyrkRole rl = (role != nullptr && role->on && role_mlp != nullptr && role_y != nullptr) ? *role : SyrkRole{0, pl.s.Gs};
   if (lv->K > 0) {

@@ -1,6 +1,6 @@
 // ba_gather128_kernel -- the gather pass specialised for the reference's feature width C = 128
 // (legacy/feat.py:251, dec.py:174) with the gradient computed on the fly from the C-channel
-// target map.  Same arithmetic as ba_gather_kernel (gather.hip); different lane mapping and
+// target map.  Same arithmetic as ba_gather_kernel (gather_generic.hip); different lane mapping and
 // scheduling:
 //
 //   * 16 lanes per pixel, 8 channels per lane: a wave instruction works on FOUR pixels (a 2x2
@@ -22,34 +22,6 @@
 #include "gather_common.hpp"
 
 namespace banet {
-
-constexpr int kC128 = 128;
-constexpr int kParStride = 8;  // src offset, texel offset, w00,w01,w10,w11 (pre-masked), mask, -
-
-__device__ __forceinline__ void morton8(int n, int& px, int& py) {  // pixel id -> position in the 8x8 patch
-  px = (n & 1) | ((n >> 1) & 2) | ((n >> 2) & 4);
-  py = ((n >> 1) & 1) | ((n >> 2) & 2) | ((n >> 3) & 4);
-}
-
-__device__ __forceinline__ int brev5(int t) { return (int)(__brev((unsigned)t) >> 27); }
-
-// carry chain of the transposing butterfly over NL levels, first lane distance S0 (cf. carry_push)
-template <int NL, int S0>
-__device__ __forceinline__ void carry_push_n(float (&pend)[NL + 1], float v, int t) {
-  bool done = false;
-#pragma unroll
-  for (int L = 0; L < NL; ++L) {
-    if (!done) {
-      if (((t >> L) & 1) == 0) {
-        pend[L] = v;
-        done = true;
-      } else {
-        v = bfly_merge(pend[L], v, S0 >> L);
-      }
-    }
-  }
-  if (!done) pend[NL] = v;
-}
 
 // KV4 = number of 128-coefficient chunks of a basis row (0: pose only; K % 4 == 0, K <= 128 KV4)
 template <int KV4>
@@ -450,17 +422,15 @@ __global__ __launch_bounds__(kBlock, BANET_G128_WAVES) void ba_gather128_kernel(
   }  // tiles
 }
 
-int launch_gather128(const GatherArgs& a, int K, hipStream_t s) {
-  dim3 grid(a.G, a.lv.B * a.pairs), block(kBlock);
-  if (K == 0)
-    hipLaunchKernelGGL((ba_gather128_kernel<0>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 128)
-    hipLaunchKernelGGL((ba_gather128_kernel<1>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 256)
-    hipLaunchKernelGGL((ba_gather128_kernel<2>), grid, block, 0, s, a);
-  else
-    return BANET_ERR_UNSUPPORTED;
-  return BANET_OK;
+int launch_gather128_step(const GatherStep& st, const GatherArgs& a, hipStream_t s) {
+#define BANET_X(kv4)                                                                                         \
+  if (st.t0 == kv4) {                                                                                        \
+    hipLaunchKernelGGL((ba_gather128_kernel<kv4>), dim3(st.gx, st.gy), dim3(st.block), st.lds, s, a);        \
+    return BANET_OK;                                                                                         \
+  }
+  BANET_GATHER_DIRECT_LIST(BANET_X)
+#undef BANET_X
+  return BANET_ERR_UNSUPPORTED;
 }
 
 }  // namespace banet

@@ -13,72 +13,9 @@
 
 namespace banet {
 
-constexpr int kC128p = 128;
 constexpr int kPatchTexels = 36;
-constexpr int kParStrideP = 8;  // src offset, texel offset, w00,w01,w10,w11 (pre-masked), mask, -
-
-__device__ __forceinline__ void morton8p(int n, int& px, int& py) {  // pixel id -> position in the 8x8 patch
-  px = (n & 1) | ((n >> 1) & 2) | ((n >> 2) & 4);
-  py = ((n >> 1) & 1) | ((n >> 2) & 2) | ((n >> 3) & 4);
-}
-
-__device__ __forceinline__ int brev5p(int t) { return (int)(__brev((unsigned)t) >> 27); }
-
-// carry chain of the transposing butterfly over NL levels, first lane distance S0 (cf. carry_push)
-template <int NL, int S0>
-__device__ __forceinline__ void carry_push_p(float (&pend)[NL + 1], float v, int t) {
-  bool done = false;
-#pragma unroll
-  for (int L = 0; L < NL; ++L) {
-    if (!done) {
-      if (((t >> L) & 1) == 0) {
-        pend[L] = v;
-        done = true;
-      } else {
-        v = bfly_merge(pend[L], v, S0 >> L);
-      }
-    }
-  }
-  if (!done) pend[NL] = v;
-}
 
 // KV4 = number of 128-coefficient chunks of a basis row (0: pose only; K % 4 == 0, K <= 128 KV4)
-typedef float v2fp __attribute__((ext_vector_type(2)));
-// channel maths of one pixel's 4-channel slice (packed fp32), accumulated into q[5] / absd[4]
-__device__ __forceinline__ void tap_math_p(const float4& f1, const float4& a0, const float4& a1, const float4& a2,
-                                           const float4& a3, const float4& b0, const float4& b1, const float4& b2,
-                                           const float4& b3, const float4& m1, const float4& m2, const float4& p1,
-                                           const float4& p2, float w00, float w01, float w10, float w11, float mk,
-                                           float (&q)[5], float* absd) {
-  const float h00 = 0.5f * w00, h01 = 0.5f * w01, h10 = 0.5f * w10, h11 = 0.5f * w11;
-  v2fp qm11 = {0.f, 0.f}, qm12 = {0.f, 0.f}, qm22 = {0.f, 0.f}, qg1 = {0.f, 0.f}, qg2 = {0.f, 0.f};
-#define BANET_V2P(v, k) (v2fp){(k) ? (v).z : (v).x, (k) ? (v).w : (v).y}
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const v2fp F1 = BANET_V2P(f1, k);
-    const v2fp A0 = BANET_V2P(a0, k), A1 = BANET_V2P(a1, k), A2 = BANET_V2P(a2, k), A3 = BANET_V2P(a3, k);
-    const v2fp B0 = BANET_V2P(b0, k), B1 = BANET_V2P(b1, k), B2 = BANET_V2P(b2, k), B3 = BANET_V2P(b3, k);
-    const v2fp M1 = BANET_V2P(m1, k), M2 = BANET_V2P(m2, k), P1 = BANET_V2P(p1, k), P2 = BANET_V2P(p2, k);
-    const v2fp f = ((A1 * w00 + A2 * w01) + B1 * w10) + B2 * w11;
-    const v2fp gx = (((A2 - A0) * h00 + (A3 - A1) * h01) + (B2 - B0) * h10) + (B3 - B1) * h11;
-    const v2fp gy = (((B1 - M1) * h00 + (B2 - M2) * h01) + (P1 - A1) * h10) + (P2 - A2) * h11;
-    const v2fp d = f - F1 * mk;
-    qm11 += gx * gx;
-    qm12 += gx * gy;
-    qm22 += gy * gy;
-    qg1 += gx * d;
-    qg2 += gy * d;
-    absd[2 * k] += fabsf(d.x);
-    absd[2 * k + 1] += fabsf(d.y);
-  }
-#undef BANET_V2P
-  q[0] += qm11.x + qm11.y;
-  q[1] += qm12.x + qm12.y;
-  q[2] += qm22.x + qm22.y;
-  q[3] += qg1.x + qg1.y;
-  q[4] += qg2.x + qg2.y;
-}
-
 // US = steps (of 4 pixels) per unit: 2 = a 4x2 pixel block, box <= 36 texels, 9 + 2 loads per lane in flight (the product
 // kernel of round 1); 4 = a 4x4 block, box <= 52 texels, 13 + 4 loads: half as many load -> LDS -> tap latency events per
 // tile, 3.06 instead of 4.4 box texels per pixel through the L1.
@@ -89,9 +26,9 @@ __device__ __forceinline__ void tap_math_p(const float4& f1, const float4& a0, c
 template <int KV4, int US, bool FS>
 __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kernel(const GatherArgs a) {
   constexpr int PT = FS ? 40 : (US == 2 ? kPatchTexels : 52), NL = (PT + 3) / 4, GL = 4 * US;   // patch texels, box loads per lane, lanes per unit
-  __shared__ __attribute__((aligned(16))) float sPar[kNumWaves][64][kParStrideP];
+  __shared__ __attribute__((aligned(16))) float sPar[kNumWaves][64][kParStride];
   __shared__ float sQ[kNumWaves][64][5];
-  __shared__ float sAbs[kNumWaves][kC128p];
+  __shared__ float sAbs[kNumWaves][kC128];
   __shared__ __attribute__((aligned(16))) float sPatch[kNumWaves][PT * 64];   // one channel half of a unit's box
   __shared__ int sGrp[kNumWaves][8][4];                                        // per unit: base offset, pw, staged texels, ph
   const banet_level_t& lv = a.lv;
@@ -105,7 +42,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = wave_id();
   const int N = lv.N, K = lv.K, H = lv.H, W = lv.W;
-  constexpr int C = kC128p;
+  constexpr int C = kC128;
   const bool dense = lv.dense != 0;
   const float* __restrict__ src_b = lv.src + (size_t)b * N * C;
   const float* __restrict__ dep_b = lv.depth + (size_t)b * N;
@@ -168,7 +105,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
     auto point_of = [&](int n, bool& valid) -> int {
       if (dense) {
         int qx, qy;
-        morton8p(n, qx, qy);
+        morton8(n, qx, qy);
         const int py = (ty << 3) + qy, px = (tx << 3) + qx;
         valid = (py < H) && (px < W);
         return valid ? py * W + px : 0;
@@ -186,7 +123,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
 
     // ---- 1. depth: D_j = D0_j + b_j . W.  A half wave reads one basis row per instruction
     // (16 B per lane); 32 row pairs go through a 5-level transposing butterfly inside each half,
-    // leaf t of half h carrying pixel h*32 + brev5p(t), so that pixel j's sum lands on lane j.
+    // leaf t of half h carrying pixel h*32 + brev5(t), so that pixel j's sum lands on lane j.
     float D = valid ? dep_b[pt] : 0.f;
     if (KV4 > 0 && !(abl & kDevAblateDepthDot)) {
       float pend[6];
@@ -194,7 +131,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
 #pragma unroll
       for (int i = 0; i < 32; ++i) {
         bool vj;
-        const int ptj = point_of(half * 32 + brev5p(i), vj);
+        const int ptj = point_of(half * 32 + brev5(i), vj);
         const float* row = bas_b + (size_t)ptj * K;
         float acc = 0.f;
 #pragma unroll
@@ -208,7 +145,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
         part[i] = acc;
       }
 #pragma unroll
-      for (int i = 0; i < 32; ++i) carry_push_p<5, 16>(pend, part[i], i);
+      for (int i = 0; i < 32; ++i) carry_push_n<5, 16>(pend, part[i], i);
       D += pend[5];
     }
 
@@ -452,7 +389,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
                          b2 = *reinterpret_cast<const float4*>(l + rs + 64), b3 = *reinterpret_cast<const float4*>(l + rs + 128);
             const float4 m1 = *reinterpret_cast<const float4*>(l - rs), m2 = *reinterpret_cast<const float4*>(l - rs + 64);
             const float4 p1 = *reinterpret_cast<const float4*>(l + 2 * rs), p2 = *reinterpret_cast<const float4*>(l + 2 * rs + 64);
-            tap_math_p(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, pa.z, pa.w, pb.x, pb.y, pb.z, qa2[t], absA);
+            tap_math(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, pa.z, pa.w, pb.x, pb.y, pb.z, qa2[t], absA);
           }
 #if BANET_TIMING == 1
           {
@@ -489,7 +426,7 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
                          b2 = *reinterpret_cast<const float4*>(rb + C), b3 = *reinterpret_cast<const float4*>(rb + 2 * C);
             const float4 m1 = *reinterpret_cast<const float4*>(rm), m2 = *reinterpret_cast<const float4*>(rm + C);
             const float4 p1 = *reinterpret_cast<const float4*>(rp), p2 = *reinterpret_cast<const float4*>(rp + C);
-            tap_math_p(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, pa.z, pa.w, pb.x, pb.y, pb.z, qa2[t], h ? absB : absA);
+            tap_math(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, pa.z, pa.w, pb.x, pb.y, pb.z, qa2[t], h ? absB : absA);
           }
         }
       }
@@ -552,25 +489,25 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
         mj[6 + i] = q.m12 * jc[i] + q.m22 * jc[6 + i];
       }
       // leaves 0..20: upper triangle of Jc^T M Jc, 21..26: Jc^T g, 27: valid count, 28..31: zero.
-      // 5 levels (lane distance 32..2) + one xor-1 add: lane l ends with leaf brev5p(l >> 1).
+      // 5 levels (lane distance 32..2) + one xor-1 add: lane l ends with leaf brev5(l >> 1).
       float pend[6];
       int o = 0;
 #pragma unroll
       for (int i = 0; i < 6; ++i)
 #pragma unroll
         for (int jj = i; jj < 6; ++jj) {
-          carry_push_p<5, 32>(pend, jc[i] * mj[jj] + jc[6 + i] * mj[6 + jj], o);
+          carry_push_n<5, 32>(pend, jc[i] * mj[jj] + jc[6 + i] * mj[6 + jj], o);
           ++o;
         }
 #pragma unroll
-      for (int i = 0; i < 6; ++i) carry_push_p<5, 32>(pend, jc[i] * q.g1 + jc[6 + i] * q.g2, 21 + i);
-      carry_push_p<5, 32>(pend, (float)(gflags & kPixInMask), 27);
+      for (int i = 0; i < 6; ++i) carry_push_n<5, 32>(pend, jc[i] * q.g1 + jc[6 + i] * q.g2, 21 + i);
+      carry_push_n<5, 32>(pend, (float)(gflags & kPixInMask), 27);
       if (a.mask_out != nullptr && valid && mine) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(gflags & kPixInMask);
 #pragma unroll
-      for (int i = 28; i < 32; ++i) carry_push_p<5, 32>(pend, 0.f, i);
+      for (int i = 28; i < 32; ++i) carry_push_n<5, 32>(pend, 0.f, i);
       float tot = pend[5];
       tot += dpp_mov<kDppXor1>(tot);
-      const int leaf = brev5p(lane >> 1);
+      const int leaf = brev5(lane >> 1);
       if ((lane & 1) == 0 && leaf < 28) part[leaf] = tot;
 
       if constexpr (KV4 > 0) {
@@ -626,36 +563,18 @@ __global__ __launch_bounds__(kBlock, BANET_G128P_WAVES) void ba_gather128p_kerne
   }  // tiles
 }
 
-int launch_gather128p(const GatherArgs& a, int K, hipStream_t s) {
-  dim3 grid(a.G, a.pairloop ? a.lv.B : a.lv.B * a.pairs), block(kBlock);
-  // kDevPatchOnePerCU (A/B experiment, experiments/README.md): 60 KB of unused dynamic LDS per workgroup -> ONE workgroup per CU
-  // (one gather wave per SIMD), the occupancy a wave-specialised gather + MFMA-accumulator kernel would leave the gather
-  size_t dyn = 0;
-  if (a.lv.flags & kDevPatchOnePerCU) {
-    dyn = 60 * 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_gather128p_kernel<1, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+int launch_gather128p_step(const GatherStep& st, const GatherArgs& a, hipStream_t s) {
+#define BANET_X(kv4, us, fs)                                                                                                       \
+  if (st.t0 == kv4 && st.t1 == us && st.t2 == (fs ? 1 : 0)) {                                                                      \
+    if (st.lds_attr)                                                                                                               \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_gather128p_kernel<kv4, us, fs>),                                 \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, st.lds);                                               \
+    hipLaunchKernelGGL((ba_gather128p_kernel<kv4, us, fs>), dim3(st.gx, st.gy), dim3(st.block), st.lds, s, a);                     \
+    return BANET_OK;                                                                                                               \
   }
-  const bool u4 = (a.lv.flags & kDevPatchUnits4) != 0;   // 4-step units (A/B, experiments/README.md)
-  const bool packed = (a.lv.flags & kDevPatchPacked) != 0;   // the packed patch with flat loads (A/B)
-  const bool small = (size_t)a.lv.H * a.lv.W * a.lv.C * 4 < ((size_t)1 << 31) && (size_t)a.lv.N * a.lv.C * 4 < ((size_t)1 << 31);
-  const bool fs = small && !packed && !dyn;          // the fixed-stride patch addresses the maps with 32-bit buffer offsets
-  if (K == 0 && fs)
-    hipLaunchKernelGGL((ba_gather128p_kernel<0, 2, true>), grid, block, 0, s, a);
-  else if (K == 0)
-    hipLaunchKernelGGL((ba_gather128p_kernel<0, 2, false>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 128 && u4)
-    hipLaunchKernelGGL((ba_gather128p_kernel<1, 4, false>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 128 && (packed || !small || dyn))
-    hipLaunchKernelGGL((ba_gather128p_kernel<1, 2, false>), grid, block, dyn, s, a);
-  else if ((K & 3) == 0 && K <= 128)
-    hipLaunchKernelGGL((ba_gather128p_kernel<1, 2, true>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 256 && fs)
-    hipLaunchKernelGGL((ba_gather128p_kernel<2, 2, true>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 256)
-    hipLaunchKernelGGL((ba_gather128p_kernel<2, 2, false>), grid, block, 0, s, a);
-  else
-    return BANET_ERR_UNSUPPORTED;
-  return BANET_OK;
+  BANET_GATHER_PATCH_LIST(BANET_X)
+#undef BANET_X
+  return BANET_ERR_UNSUPPORTED;
 }
 
 }  // namespace banet

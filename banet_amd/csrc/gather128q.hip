@@ -25,8 +25,6 @@
 
 namespace banet {
 
-constexpr int kC128q = 128;
-
 template <int V>
 struct QC {
   static constexpr int value = V;
@@ -49,7 +47,7 @@ __device__ __forceinline__ float4 f4(const f32x4& v) { return make_float4(v[0], 
 // KV4 = number of 128-coefficient chunks of a basis row (0: pose only; K % 4 == 0, K <= 128 KV4)
 template <int KV4>
 __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherArgs a) {
-  __shared__ float sAbs[kNumWaves][kC128q];
+  __shared__ float sAbs[kNumWaves][kC128];
   const banet_level_t& lv = a.lv;
   const int vb = blockIdx.y;                   // vb = (window, pair)
   const int b = vb / a.pairs;
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherAr
   const int lane = threadIdx.x & 63;
   const int w = wave_id();
   const int N = lv.N, K = lv.K, H = lv.H, W = lv.W;
-  constexpr int C = kC128q;
+  constexpr int C = kC128;
   const float* __restrict__ tgt_b = lv.tgt + (size_t)vb * H * W * C;
   const float* __restrict__ src_b = lv.src + (size_t)b * N * C;
   const float* __restrict__ dep_b = lv.depth + (size_t)b * N;
@@ -151,7 +149,7 @@ __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherAr
       for (int e = 0; e < 4; ++e) absd[u][e] = 0.f;
     auto compute = [&](const QTaps& cur, auto uc) __attribute__((always_inline)) {
       constexpr int u = decltype(uc)::value;
-      tap_math_s(f4(cur.f1), f4(cur.a0), f4(cur.a1), f4(cur.a2), f4(cur.a3), f4(cur.b0), f4(cur.b1), f4(cur.b2), f4(cur.b3),
+      tap_math(f4(cur.f1), f4(cur.a0), f4(cur.a1), f4(cur.a2), f4(cur.a3), f4(cur.b0), f4(cur.b1), f4(cur.b2), f4(cur.b3),
                  f4(cur.m1), f4(cur.m2), f4(cur.p1), f4(cur.p2), w00, w01, w10, w11, mk, qq, absd[u]);
     };
     {
@@ -226,17 +224,17 @@ __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherAr
 #pragma unroll
         for (int jj = i; jj < 6; ++jj) {
           const float v = jc[i] * mj[jj] + jc[6 + i] * mj[6 + jj];
-          carry_push_s<5, 32>(pend, own ? v : 0.f, o);
+          carry_push_n<5, 32>(pend, own ? v : 0.f, o);
           ++o;
         }
 #pragma unroll
-      for (int i = 0; i < 6; ++i) carry_push_s<5, 32>(pend, own ? jc[i] * qv.g1 + jc[6 + i] * qv.g2 : 0.f, 21 + i);
-      carry_push_s<5, 32>(pend, own ? (float)(ge.flags & kPixInMask) : 0.f, 27);
+      for (int i = 0; i < 6; ++i) carry_push_n<5, 32>(pend, own ? jc[i] * qv.g1 + jc[6 + i] * qv.g2 : 0.f, 21 + i);
+      carry_push_n<5, 32>(pend, own ? (float)(ge.flags & kPixInMask) : 0.f, 27);
 #pragma unroll
-      for (int i = 28; i < 32; ++i) carry_push_s<5, 32>(pend, 0.f, i);
+      for (int i = 28; i < 32; ++i) carry_push_n<5, 32>(pend, 0.f, i);
       float tot = pend[5];
       tot += dpp_mov<kDppXor1>(tot);
-      const int leaf = brev5s(lane >> 1);
+      const int leaf = brev5(lane >> 1);
       if ((lane & 1) == 0 && leaf < 28) part[leaf] = tot;
       if (a.mask_out != nullptr && valid && own) a.mask_out[(size_t)vb * N + pt] = (unsigned char)(ge.flags & kPixInMask);
       if constexpr (KV4 > 0) {
@@ -273,17 +271,15 @@ __global__ __launch_bounds__(kBlock, 2) void ba_gather128q_kernel(const GatherAr
   }  // items
 }
 
-int launch_gather128q(const GatherArgs& a, int K, hipStream_t s) {
-  dim3 grid(a.G, a.lv.B * a.pairs), block(kBlock);
-  if (K == 0)
-    hipLaunchKernelGGL((ba_gather128q_kernel<0>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 128)
-    hipLaunchKernelGGL((ba_gather128q_kernel<1>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 256)
-    hipLaunchKernelGGL((ba_gather128q_kernel<2>), grid, block, 0, s, a);
-  else
-    return BANET_ERR_UNSUPPORTED;
-  return BANET_OK;
+int launch_gather128q_step(const GatherStep& st, const GatherArgs& a, hipStream_t s) {
+#define BANET_X(kv4)                                                                                         \
+  if (st.t0 == kv4) {                                                                                        \
+    hipLaunchKernelGGL((ba_gather128q_kernel<kv4>), dim3(st.gx, st.gy), dim3(st.block), st.lds, s, a);       \
+    return BANET_OK;                                                                                         \
+  }
+  BANET_GATHER_QUAD_LIST(BANET_X)
+#undef BANET_X
+  return BANET_ERR_UNSUPPORTED;
 }
 
 }  // namespace banet

@@ -24,19 +24,12 @@
 //   * pixel rows whose footprint does not fit the window (local scale > ~1.12, a depth discontinuity) read their taps
 //     directly; pixels on the image rim take the generic slow routine (as in the other C = 128 kernels).
 // Same arithmetic per pixel as ba_gather128_kernel; the channel sums are added slice by slice (different rounding order).
-#include <cstdlib>
-
 #include "quad_common.hpp"
 #include "strip_plan.hpp"
 static_assert(banet::kStripSegW == banet::kStripW && banet::kStripSegH == banet::kStripH && banet::kStripMinW == banet::kWinTex, "plan.hpp sizes the strip launch by these");
 
-#ifndef BANET_STRIP_OPT_DEFAULT
-#define BANET_STRIP_OPT_DEFAULT 0
-#endif
-
 namespace banet {
 
-constexpr int kC128s = 128;
 constexpr int kSBlock = 128;                       // 2 waves per workgroup, 4 workgroups per CU (LDS: 2 x 19.9 KB)
 constexpr int kSWaves = kSBlock / kWave;
 constexpr int kWinFloats = kWinRows * kWinTex * 32;
@@ -172,7 +165,7 @@ struct IC {
 // KV4 = number of 128-coefficient chunks of a basis row (0: pose only; K % 4 == 0, K <= 128 KV4)
 // NCH = chunks per segment: 2 (16 x 8 pixels, 11/8 x: mid-size launches that have too few 16-row segments per wave), 4 (the default),
 // 8 (16 x 32 pixels, target rows fetched 35/32 x) where a launch has enough of them to fill the
-// chip evenly, 4 (16 x 16 pixels, 19/16 x) on launches with fewer, coarser items (gather.hip::plan_gather)
+// chip evenly, 4 (16 x 16 pixels, 19/16 x) on launches with fewer, coarser items (plan.hpp: choose_strip)
 // FP ("frame-parallel", multi-frame windows): a workgroup is `pairs` waves that process the SAME segment at the same time, wave p
 // against target frame p.  The key frame's data is then fetched from HBM once per window instead of once per target frame: the
 // depth dot (the basis rows) is divided among the waves and shared through LDS, and the source rows, which every wave still
@@ -181,10 +174,10 @@ struct IC {
 // time the chip has moved hundreds of MB: 29 % of a 5-frame window's traffic.)  Two workgroup barriers per segment (item
 // broadcast, depth hand-over), none inside the counted section.
 extern __shared__ __attribute__((aligned(16))) float sDynS[];
-constexpr int kSWaveLdsFloats = kWinFloats + kC128s;     // per wave: the rolling window + row statistics / sum|d|
-inline size_t strip_fp_lds_bytes(int pairs, int nch) { return ((size_t)pairs * kSWaveLdsFloats + (size_t)nch * 64 + 4) * sizeof(float); }
+constexpr int kSWaveLdsFloats = kWinFloats + kC128;     // per wave: the rolling window + row statistics / sum|d|
+static_assert(kSWaveLdsFloats == kStripWaveLdsFloats, "plan.hpp sizes the frame-parallel workgroup's LDS (strip_fp_lds_bytes) by this");
 
-// OPT (development A/B, BANET_STRIP_OPT): bit 0 = both 16-byte pieces' window reads of a step issued before the first piece's
+// OPT (development A/B, measured neutral: profiles/r05_run2_*; no launch selects a variant any more, only OPT = 0 is built): bit 0 = both 16-byte pieces' window reads of a step issued before the first piece's
 // channel maths (the second LDS round trip hidden behind it); bit 1 = one M0 write per window row (glds_row)
 template <int KV4, int NCH, bool FP, int OPT = 0>
 __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vgpr(kStripVgprs / 2))) void ba_gather128s_kernel(const GatherArgs a) {
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
   constexpr int NH = (NCH + 3) / 4;      // groups of four chunks
   constexpr int CPG = NCH < 4 ? NCH : 4; // chunks per group (NCH = 2: 8-row segments for mid-size launches, one half-filled group)
   __shared__ __attribute__((aligned(16))) float sWinS[FP ? 1 : kSWaves][FP ? 4 : kWinFloats];    // the rolling window: [slot][texel][32 channels]
-  __shared__ __attribute__((aligned(16))) float sScrS[FP ? 1 : kSWaves][FP ? 4 : kC128s];        // row statistics (plan input), later C x sum|d|
+  __shared__ __attribute__((aligned(16))) float sScrS[FP ? 1 : kSWaves][FP ? 4 : kC128];        // row statistics (plan input), later C x sum|d|
   const banet_level_t& lv = a.lv;
   const int b = blockIdx.y;
   if (a.active != nullptr && a.active[(size_t)b * a.active_stride] == 0) return;
@@ -205,7 +198,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
   [[maybe_unused]] float* const sDep = sDynS + (size_t)nw * kSWaveLdsFloats;        // FP: [NCH][64] depths of the segment
   [[maybe_unused]] int* const sItem = reinterpret_cast<int*>(sDep + NCH * 64);      // FP: [2] the segment index, ping-pong
   const int N = lv.N, K = lv.K, H = lv.H, W = lv.W;
-  constexpr int C = kC128s;
+  constexpr int C = kC128;
   const float* __restrict__ src_b = lv.src + (size_t)b * N * C;
   const float* __restrict__ dep_b = lv.depth + (size_t)b * N;
   const float* __restrict__ bas_b = KV4 ? lv.basis + (size_t)b * N * K : nullptr;
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
           // leaf i of half h ends on lane 32 h + brev5(i), which owns pixel (row ld & 3, column ld >> 2) of the chunk
-          const int ld = half * 32 + brev5s(RB * hb + i);
+          const int ld = half * 32 + brev5(RB * hb + i);
           const int jx = sx * kStripW + (ld >> 2), jy = sy * SEGH + 4 * c + (ld & 3);
           const bool vj = (jx < W) && (jy < H);
 #if defined(BANET_ABLATE_STRIP) && BANET_ABLATE_STRIP >= 2
@@ -306,7 +299,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
           for (int kc = 0; kc < KV4; ++kc)
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc = fmaf(bv[BUF][i][kc][e], wreg[kc][e], acc);   // k >= K: wreg is 0
-          carry_push_s<5, 16>(pend, acc, RB * hb + i);
+          carry_push_n<5, 16>(pend, acc, RB * hb + i);
         }
       };
       if constexpr (FP) {
@@ -589,9 +582,9 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
                 rd(tA, 4 * jA);
                 rd(tB, 4 * jB);
                 __builtin_amdgcn_sched_barrier(0);
-                tap_math_s(fA, tA[0], tA[1], tA[2], tA[3], tA[4], tA[5], tA[6], tA[7], tA[8], tA[9], tA[10], tA[11], w00, w01, w10, w11, mk, qq, absA);
+                tap_math(fA, tA[0], tA[1], tA[2], tA[3], tA[4], tA[5], tA[6], tA[7], tA[8], tA[9], tA[10], tA[11], w00, w01, w10, w11, mk, qq, absA);
                 __builtin_amdgcn_sched_barrier(0);
-                tap_math_s(fB, tB[0], tB[1], tB[2], tB[3], tB[4], tB[5], tB[6], tB[7], tB[8], tB[9], tB[10], tB[11], w00, w01, w10, w11, mk, qq, absB);
+                tap_math(fB, tB[0], tB[1], tB[2], tB[3], tB[4], tB[5], tB[6], tB[7], tB[8], tB[9], tB[10], tB[11], w00, w01, w10, w11, mk, qq, absB);
               } else {
 #pragma unroll
               for (int hp = 0; hp < 2; ++hp) {      // the lane's two 16-byte pieces of every tap
@@ -609,9 +602,9 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
                 if (hp) ts_ldsB += (float)(tl1 - tlm); else ts_ldsA += (float)(tl1 - tl0);
 #endif
                 if (hp)
-                  tap_math_s(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absB);
+                  tap_math(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absB);
                 else
-                  tap_math_s(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absA);
+                  tap_math(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absA);
 #if defined(BANET_TIMING) && BANET_TIMING >= 4
                 asm volatile("" ::"v"(qq[0]), "v"(qq[4]) : "memory");
                 BANET_TICK(tl2);
@@ -642,9 +635,9 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
                 const float4 m1 = *reinterpret_cast<const float4*>(rm), m2 = *reinterpret_cast<const float4*>(rm + C);
                 const float4 p1 = *reinterpret_cast<const float4*>(rp), p2 = *reinterpret_cast<const float4*>(rp + C);
                 if (hp)
-                  tap_math_s(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absB);
+                  tap_math(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absB);
                 else
-                  tap_math_s(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absA);
+                  tap_math(f1, a0, a1, a2, a3, b0, b1, b2, b3, m1, m2, p1, p2, w00, w01, w10, w11, mk, qq, absA);
               }
             }
 #pragma unroll
@@ -772,12 +765,12 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
         // 32..2) + one xor-1 add: lane l ends with leaf brev5(l >> 1)
         float pend[6];
 #pragma unroll
-        for (int i = 0; i < 28; ++i) carry_push_s<5, 32>(pend, accp[i], i);
+        for (int i = 0; i < 28; ++i) carry_push_n<5, 32>(pend, accp[i], i);
 #pragma unroll
-        for (int i = 28; i < 32; ++i) carry_push_s<5, 32>(pend, 0.f, i);
+        for (int i = 28; i < 32; ++i) carry_push_n<5, 32>(pend, 0.f, i);
         float tot = pend[5];
         tot += dpp_mov<kDppXor1>(tot);
-        const int leaf = brev5s(lane >> 1);
+        const int leaf = brev5(lane >> 1);
         if ((lane & 1) == 0 && leaf < 28) part[leaf] = tot;
       }
       // ---- 5. the segment's C x sum|d| ----------------------------------------------------------------------------------------
@@ -822,71 +815,18 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
   }  // items
 }
 
-// development A/B (builds with -DBANET_STRIP_OPT_VARIANTS only; measured neutral, profiles/r05_run2_*): BANET_STRIP_OPT selects the
-// OPT variant of the K <= 128, 16-row-segment kernels (read once)
-static int strip_opt() {
-  static const int v = [] {
-    const char* e = std::getenv("BANET_STRIP_OPT");
-    const int x = e ? std::atoi(e) : BANET_STRIP_OPT_DEFAULT;
-    return x >= 0 && x <= 3 ? x : 0;
-  }();
-  return v;
-}
-
-int launch_gather128s(const GatherArgs& a, int K, hipStream_t s) {
-  dim3 grid(a.G, a.lv.B), block(kSBlock);
-  const bool tall = a.seg_h == 32, low = a.seg_h == 8;
-  if (a.seg_h != 32 && a.seg_h != 16 && a.seg_h != 8) return BANET_ERR_INVALID_ARG;
-  if (a.strip_fp) {    // frame-parallel workgroups: `pairs` waves, dynamic LDS (16-row segments only)
-    if (tall || low || a.pairs < 2 || a.pairs > 7) return BANET_ERR_INVALID_ARG;
-    const size_t shm = strip_fp_lds_bytes(a.pairs, 4);
-    block = dim3(64 * a.pairs);
-#define BANET_LAUNCH_FP(KV4)                                                                                              \
-  do {                                                                                                                    \
-    if (shm > 64 * 1024)                                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_gather128s_kernel<KV4, 4, true>),                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                                    \
-    hipLaunchKernelGGL((ba_gather128s_kernel<KV4, 4, true>), grid, block, shm, s, a);                                     \
-  } while (0)
-#define BANET_LAUNCH_FPO(OPT)                                                                                             \
-  do {                                                                                                                    \
-    if (shm > 64 * 1024)                                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_gather128s_kernel<1, 4, true, OPT>),                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                                    \
-    hipLaunchKernelGGL((ba_gather128s_kernel<1, 4, true, OPT>), grid, block, shm, s, a);                                  \
-  } while (0)
-    [[maybe_unused]] const int opt = strip_opt();
-    if (K == 0) BANET_LAUNCH_FP(0);
-#ifdef BANET_STRIP_OPT_VARIANTS
-    else if ((K & 3) == 0 && K <= 128 && opt == 1) BANET_LAUNCH_FPO(1);
-    else if ((K & 3) == 0 && K <= 128 && opt == 2) BANET_LAUNCH_FPO(2);
-    else if ((K & 3) == 0 && K <= 128 && opt == 3) BANET_LAUNCH_FPO(3);
-#endif
-    else if ((K & 3) == 0 && K <= 128) BANET_LAUNCH_FP(1);
-    else if ((K & 3) == 0 && K <= 256) BANET_LAUNCH_FP(2);
-    else return BANET_ERR_UNSUPPORTED;
-#undef BANET_LAUNCH_FP
-#undef BANET_LAUNCH_FPO
-    return BANET_OK;
+int launch_gather128s_step(const GatherStep& st, const GatherArgs& a, hipStream_t s) {
+#define BANET_X(kv4, nch, fp)                                                                                                      \
+  if (st.t0 == kv4 && st.t1 == nch && st.t2 == (fp ? 1 : 0)) {                                                                     \
+    if (st.lds_attr)                                                                                                               \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_gather128s_kernel<kv4, nch, fp>),                                \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, st.lds);                                               \
+    hipLaunchKernelGGL((ba_gather128s_kernel<kv4, nch, fp>), dim3(st.gx, st.gy), dim3(st.block), st.lds, s, a);                    \
+    return BANET_OK;                                                                                                               \
   }
-#define BANET_LAUNCH_S(KV4)                                                                     \
-  do {                                                                                          \
-    if (tall) hipLaunchKernelGGL((ba_gather128s_kernel<KV4, 8, false>), grid, block, 0, s, a);  \
-    else if (low) hipLaunchKernelGGL((ba_gather128s_kernel<KV4, 2, false>), grid, block, 0, s, a); \
-    else hipLaunchKernelGGL((ba_gather128s_kernel<KV4, 4, false>), grid, block, 0, s, a);       \
-  } while (0)
-  [[maybe_unused]] const int opt = strip_opt();
-  if (K == 0) BANET_LAUNCH_S(0);
-#ifdef BANET_STRIP_OPT_VARIANTS
-  else if ((K & 3) == 0 && K <= 128 && !tall && !low && opt == 1) hipLaunchKernelGGL((ba_gather128s_kernel<1, 4, false, 1>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 128 && !tall && !low && opt == 2) hipLaunchKernelGGL((ba_gather128s_kernel<1, 4, false, 2>), grid, block, 0, s, a);
-  else if ((K & 3) == 0 && K <= 128 && !tall && !low && opt == 3) hipLaunchKernelGGL((ba_gather128s_kernel<1, 4, false, 3>), grid, block, 0, s, a);
-#endif
-  else if ((K & 3) == 0 && K <= 128) BANET_LAUNCH_S(1);
-  else if ((K & 3) == 0 && K <= 256) BANET_LAUNCH_S(2);
-  else return BANET_ERR_UNSUPPORTED;
-#undef BANET_LAUNCH_S
-  return BANET_OK;
+  BANET_GATHER_STRIP_LIST(BANET_X)
+#undef BANET_X
+  return BANET_ERR_UNSUPPORTED;
 }
 
 }  // namespace banet

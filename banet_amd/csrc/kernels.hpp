@@ -12,16 +12,16 @@ constexpr int kUStrideS = 8;    // per-pixel record: u0..u5, s, r
 // device is visible, e.g. the host-only plan / workspace arithmetic of the CPU tests).  The launch plans size their grids by it.
 int num_cus();
 
-// ---- gather.hip ------------------------------------------------------------------------
-// (GatherPlan / plan_gather: plan.hpp)
+// ---- gather.hip (driver; the step list: plan.hpp, kernels: gather_generic / gather128 / 128p / 128s / 128q.hip) ----------
+// (GatherPlan / plan_gather / plan_gather_steps: plan.hpp)
 // prepare (reset the tile queue) -> launch (the gather kernel alone: this is what the profiler times)
-// -> finish (fold the tile partials); `reduced` returns the rows ba_reduce2_kernel should read
-void prepare_gather(const banet_level_t* lv, const GatherPlan& pl, float* partials, hipStream_t s);
-int launch_gather(const banet_level_t* lv, const GatherPlan& pl, const float* R, const float* T, const float* Wc,
+// -> finish (fold the tile partials; returns the rows ba_reduce2_kernel should read): each enqueues its steps of `steps`
+void prepare_gather(const GatherSteps& steps, const GatherPlan& pl, float* partials, hipStream_t s);
+int launch_gather(const GatherSteps& steps, const banet_level_t* lv, const GatherPlan& pl, const float* R, const float* T, const float* Wc,
                   const int32_t* active, int active_stride, float* rec, float* partials, hipStream_t s,
                   unsigned char* mask_out = nullptr);
-const float* finish_gather(const banet_level_t* lv, const GatherPlan& pl, const int32_t* active, int active_stride,
-                           float* partials, hipStream_t s);
+const float* finish_gather(const GatherSteps& steps, const banet_level_t* lv, const GatherPlan& pl, const int32_t* active,
+                           int active_stride, float* partials, hipStream_t s);
 
 // ---- syrk.hip (driver; the step list: plan.hpp, kernels: syrk_lds / _mfma32 / _bf16x6 / _wide / _stats.hip) -------------
 struct MlpRole {        // one extra workgroup per window of the SYRK launch evaluates the lambda MLP (mlp.hpp); y == nullptr: off

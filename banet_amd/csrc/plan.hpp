@@ -1,9 +1,10 @@
 // The host-side launch plans of one assembly pass: which gather / SYRK kernel runs, on what grid, how many partial rows it
-// writes (the summation tree) and where every buffer lies in the workspace; for the SYRK also every launch of a pass as a list of
-// steps (plan_syrk_steps: pre-passes, kernel instantiation, job, grid, LDS -- syrk.hip walks it), the statistics mode of a pass
-// (SyrkStats), the lambda-MLP role decision (plan_syrk_role) and the lists of compiled SYRK instantiations.  Host-only, plain C++17
-// (no HIP include): the .hip files take the plans AND the occupancy numbers of their __launch_bounds__ from here, and
-// tests/native/plan_host.cpp compiles this header with g++ to pin every decision (tests/test_plan_cpu.py, tests/test_syrk_steps_cpu.py).
+// writes (the summation tree) and where every buffer lies in the workspace; every launch of a gather pass and of a SYRK pass as a list
+// of steps (plan_gather_steps: queue zeroing, kernel instantiation, grid, block, LDS, fold -- gather.hip walks it; plan_syrk_steps:
+// pre-passes, kernel instantiation, job, grid, LDS -- syrk.hip walks it), the statistics mode of a pass (SyrkStats), the lambda-MLP role
+// decision (plan_syrk_role) and the lists of compiled gather / SYRK instantiations.  Host-only, plain C++17 (no HIP include): the .hip
+// files take the plans AND the occupancy numbers of their __launch_bounds__ from here, and tests/native/plan_host.cpp compiles this header
+// with g++ to pin every decision (tests/test_plan_cpu.py, tests/test_gather_steps_cpu.py, tests/test_syrk_steps_cpu.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -77,6 +78,11 @@ constexpr int kGenericBlocksPerCU = BANET_GATHER_WAVES;  // ba_gather_kernel: la
 constexpr int kC128BlocksPerCU = BANET_G128_WAVES;       // ba_gather128_kernel: launch bounds (LDS: 18 KB)
 constexpr int kPatchBlocksPerCU = BANET_G128P_WAVES;     // ba_gather128p_kernel: launch bounds
 
+// ba_gather128s_kernel's LDS: per wave the rolling window (7 rows x kStripMinW texels x 32 channels) + 128 floats of row statistics
+// (= kSWaveLdsFloats, asserted in gather128s.hip); a frame-parallel workgroup holds `pairs` of them + [nch][64] depths + 4 words
+constexpr int kStripWaveLdsFloats = 7 * kStripMinW * 32 + 128;
+inline size_t strip_fp_lds_bytes(int pairs, int nch) { return ((size_t)pairs * kStripWaveLdsFloats + (size_t)nch * 64 + 4) * sizeof(float); }
+
 namespace plan_detail {
 
 inline bool use_c128(const banet_level_t* lv) {
@@ -112,7 +118,7 @@ inline bool choose_strip(const banet_level_t* lv, int kCUs, int Bsel, GatherPlan
   // multi-frame windows: frame-parallel workgroups (gather128s.hip, FP) -- `pairs` waves per segment, so a launch has
   // 2048 / pairs resident work-item slots instead of 2048.  kDevStripFrameLoop: the frames looped over inside one wave (A/B).
   const bool fp = np >= 2 && np <= 7 && segh == kStripSegH / 2 && !(lv->flags & kDevStripFrameLoop);
-  const int fp_wg_per_cu = fp ? (int)std::min<size_t>(8 / np, (size_t)(160 * 1024) / (((size_t)np * (7 * 21 * 32 + 128) + 4 * 64 + 4) * 4)) : 0;
+  const int fp_wg_per_cu = fp ? (int)std::min<size_t>(8 / np, (size_t)(160 * 1024) / strip_fp_lds_bytes(np, 4)) : 0;
   const long long slots = fp ? (long long)kCUs * fp_wg_per_cu : (long long)kCUs * 8;
   if (!((long long)sxn * syn * Bsel >= 4LL * slots || low || (lv->flags & kDevForceStripGather))) return false;
   pl->strip = segh;
@@ -252,6 +258,139 @@ inline int plan_gather(const banet_level_t* lv, int kCUs, GatherPlan* pl) {
   if (!choose_strip(lv, kCUs, Bsel, pl) && !choose_quad(lv, kCUs, Bsel, pl)) choose_tile(lv, kCUs, Bsel, pl);
   // 4. the partial buffer
   layout_partials(pl, lv);
+  return BANET_OK;
+}
+
+// ---- the gather launch as data --------------------------------------------------------------
+// What gather.hip enqueues for one pass: plan_gather_steps lists every launch in order, with its kernel, template parameters, grid,
+// block and LDS; the driver walks the list and decides nothing (tests/native/plan_host.cpp dumps it, tests/test_gather_steps_cpu.py
+// pins it).
+
+// The compiled instantiations, each list written once: the per-file launch code instantiates from these lists, plan_gather_steps takes
+// "supported" from them and the host test program enumerates them.
+#define BANET_GATHER_GENERIC_K_(X, vec, ch, grad) X(vec, ch, grad, 1, 0) X(vec, ch, grad, 2, 1) X(vec, ch, grad, 2, 2) X(vec, ch, grad, 1, 1) X(vec, ch, grad, 1, 2)
+#define BANET_GATHER_GENERIC_C_(X, grad) \
+  BANET_GATHER_GENERIC_K_(X, 2, 1, grad) BANET_GATHER_GENERIC_K_(X, 2, 2, grad) BANET_GATHER_GENERIC_K_(X, 1, 1, grad) BANET_GATHER_GENERIC_K_(X, 1, 2, grad)
+#define BANET_GATHER_GENERIC_LIST(X) BANET_GATHER_GENERIC_C_(X, false) BANET_GATHER_GENERIC_C_(X, true)   // ba_gather_kernel<VEC, CH, GRAD, KVEC, KCH>: 4 x 2 x 5
+#define BANET_GATHER_DIRECT_LIST(X) X(0) X(1) X(2)                                                         // ba_gather128_kernel<KV4>
+#define BANET_GATHER_PATCH_LIST(X) X(0, 2, true) X(0, 2, false) X(1, 4, false) X(1, 2, false) X(1, 2, true) X(2, 2, true) X(2, 2, false)   // ba_gather128p_kernel<KV4, US, FS>
+#define BANET_GATHER_STRIP_KV4_(X, kv4) X(kv4, 2, false) X(kv4, 4, false) X(kv4, 8, false) X(kv4, 4, true)
+#define BANET_GATHER_STRIP_LIST(X) BANET_GATHER_STRIP_KV4_(X, 0) BANET_GATHER_STRIP_KV4_(X, 1) BANET_GATHER_STRIP_KV4_(X, 2)           // ba_gather128s_kernel<KV4, NCH, FP>
+#define BANET_GATHER_QUAD_LIST(X) X(0) X(1) X(2)                                                           // ba_gather128q_kernel<KV4>
+
+enum GatherStepKind {
+  kGatherStepZero = 0,   // zero_iters_kernel on the tile-queue heads (t0 words)
+  kGatherStepGeneric,    // ba_gather_kernel<t0 = VEC, t1 = CH, t2 = GRAD, t3 = KVEC, t4 = KCH>
+  kGatherStepDirect,     // ba_gather128_kernel<t0 = KV4>
+  kGatherStepPatch,      // ba_gather128p_kernel<t0 = KV4, t1 = US, t2 = FS>
+  kGatherStepStrip,      // ba_gather128s_kernel<t0 = KV4, t1 = NCH, t2 = FP>
+  kGatherStepQuad,       // ba_gather128q_kernel<t0 = KV4>
+  kGatherStepFold,       // ba_fold_kernel
+};
+struct GatherStep {
+  int kind;                  // GatherStepKind
+  int t0, t1, t2, t3, t4;    // template parameters (kGatherStepZero: t0 = words to zero)
+  int gx, gy, block;
+  int lds;                   // dynamic LDS bytes
+  int lds_attr;              // 1: the launch sets the function attribute for its dynamic LDS
+};
+constexpr int kGatherMaxSteps = 3;   // zero, the gather kernel, fold
+struct GatherSteps {
+  int n;
+  GatherStep step[kGatherMaxSteps];
+};
+
+namespace plan_detail {
+
+inline bool gather_step_compiled(const GatherStep& st) {
+  bool found = false;
+  switch (st.kind) {
+    case kGatherStepGeneric:
+#define BANET_X(vec, ch, grad, kvec, kch) found = found || (st.t0 == vec && st.t1 == ch && st.t2 == (grad ? 1 : 0) && st.t3 == kvec && st.t4 == kch);
+      BANET_GATHER_GENERIC_LIST(BANET_X)
+#undef BANET_X
+      return found;
+    case kGatherStepDirect:
+#define BANET_X(kv4) found = found || st.t0 == kv4;
+      BANET_GATHER_DIRECT_LIST(BANET_X)
+#undef BANET_X
+      return found;
+    case kGatherStepPatch:
+#define BANET_X(kv4, us, fs) found = found || (st.t0 == kv4 && st.t1 == us && st.t2 == (fs ? 1 : 0));
+      BANET_GATHER_PATCH_LIST(BANET_X)
+#undef BANET_X
+      return found;
+    case kGatherStepStrip:
+#define BANET_X(kv4, nch, fp) found = found || (st.t0 == kv4 && st.t1 == nch && st.t2 == (fp ? 1 : 0));
+      BANET_GATHER_STRIP_LIST(BANET_X)
+#undef BANET_X
+      return found;
+    case kGatherStepQuad:
+#define BANET_X(kv4) found = found || st.t0 == kv4;
+      BANET_GATHER_QUAD_LIST(BANET_X)
+#undef BANET_X
+      return found;
+  }
+  return true;   // the zeroing and the fold are not templates
+}
+
+// 128-coefficient chunks of a basis row in the C = 128 kernels (K % 4 == 0, K <= 256), -1: no such kernel
+inline int gather_kv4(int K) { return K == 0 ? 0 : ((K & 3) == 0 && K <= 128) ? 1 : ((K & 3) == 0 && K <= 256) ? 2 : -1; }
+
+}  // namespace plan_detail
+
+// The launches of one gather pass, in order.  pl: plan_gather's for lv; reset_queue: the pass zeroes the tile-queue heads first (the LM
+// loop's later iterations find them zeroed by the solve kernel).  BANET_ERR_UNSUPPORTED (and an empty list) where the gather kernel
+// is not compiled: the generic kernel at odd C above 128 or odd K above 128.
+inline int plan_gather_steps(const banet_level_t* lv, const GatherPlan& pl, bool reset_queue, GatherSteps* out) {
+  using namespace plan_detail;
+  *out = GatherSteps{};
+  const int pairs = npairs(lv), VB = lv->B * pairs, C = lv->C, K = lv->K;
+  GatherStep k{kGatherStepGeneric, 0, 0, 0, 0, 0, pl.G, VB, kBlock, 0, 0};
+  if (!pl.c128) {
+    // two channels (coefficients) per lane where the count is even, one chunk of 64 lanes where it fits: up to 256 even, 128 odd
+    const bool ceven = (C & 1) == 0, keven = (K & 1) == 0;
+    k.t0 = ceven ? 2 : 1;
+    k.t1 = C <= 64 * k.t0 ? 1 : C <= 128 * k.t0 ? 2 : 0;
+    k.t2 = lv->tgt_has_grad ? 1 : 0;
+    k.t3 = (K > 0 && keven) ? 2 : 1;
+    k.t4 = K == 0 ? 0 : K <= 64 * k.t3 ? 1 : K <= 128 * k.t3 ? 2 : -1;
+  } else if (pl.quad) {
+    k.kind = kGatherStepQuad;
+    k.t0 = gather_kv4(K);
+  } else if (pl.strip) {
+    // frame-parallel workgroups: `pairs` waves on dynamic LDS, 16-row segments only
+    if ((pl.strip != 8 && pl.strip != 16 && pl.strip != 32) || (pl.strip_fp && (pl.strip != 16 || pairs < 2 || pairs > 7))) return BANET_ERR_INVALID_ARG;
+    k.kind = kGatherStepStrip;
+    k.t0 = gather_kv4(K);
+    k.t1 = pl.strip / 4;   // NCH: 4-row chunks per segment
+    k.t2 = pl.strip_fp ? 1 : 0;
+    k.gy = lv->B;
+    k.block = pl.strip_fp ? kWave * pairs : 128;
+    k.lds = pl.strip_fp ? (int)strip_fp_lds_bytes(pairs, 4) : 0;
+    k.lds_attr = k.lds > 64 * 1024 ? 1 : 0;
+  } else if (pl.patch) {
+    const int kv4 = gather_kv4(K);
+    // kDevPatchOnePerCU (A/B experiment, experiments/README.md): 60 KB of unused dynamic LDS per workgroup -> ONE workgroup per CU
+    // (one gather wave per SIMD), the occupancy a wave-specialised gather + MFMA-accumulator kernel would leave the gather;
+    // kDevPatchUnits4: 4-step units, kDevPatchPacked: the packed patch with flat loads (A/B, experiments/README.md)
+    const bool one = (lv->flags & kDevPatchOnePerCU) != 0, u4 = (lv->flags & kDevPatchUnits4) != 0, packed = (lv->flags & kDevPatchPacked) != 0;
+    // the fixed-stride patch addresses the maps with 32-bit buffer offsets
+    const bool small = (size_t)lv->H * lv->W * C * 4 < ((size_t)1 << 31) && (size_t)lv->N * C * 4 < ((size_t)1 << 31);
+    k.kind = kGatherStepPatch;
+    k.t0 = kv4;
+    k.t1 = (kv4 == 1 && u4) ? 4 : 2;
+    k.t2 = (small && !packed && !one && k.t1 == 2) ? 1 : 0;
+    k.gy = pl.pairloop ? lv->B : VB;
+    if (kv4 == 1 && k.t1 == 2 && one) k.lds = 60 * 1024, k.lds_attr = 1;   // the one instantiation the experiment runs on
+  } else {
+    k.kind = kGatherStepDirect;
+    k.t0 = gather_kv4(K);
+  }
+  if (!gather_step_compiled(k)) return BANET_ERR_UNSUPPORTED;
+  if (pl.c128 && reset_queue) out->step[out->n++] = GatherStep{kGatherStepZero, VB * 8, 0, 0, 0, 0, (VB * 8 + 63) / 64, 1, 64, 0, 0};
+  out->step[out->n++] = k;
+  if (pl.frows != pl.rows) out->step[out->n++] = GatherStep{kGatherStepFold, 0, 0, 0, 0, 0, pl.frows, VB, 256, 0, 0};
   return BANET_OK;
 }
 

@@ -3,7 +3,7 @@
 // For every window b, target frame f (banet_level_t.pairs) and point n (file:line citations are the reference's):
 //   D = D0 + Bs.W                         bundlenet.py:208      once per point, reused for every frame of the window
 //   X = (R_f p) D + T_f ; px, py ; mask   bundlenet.py:209-224,155 / legacy/ba.py:239-251 -- the float32 statements of the
-//                                         gathers: strip_geometry (quad_common.hpp) on a dense level, gather.hip's on sparse points
+//                                         gathers: strip_geometry (quad_common.hpp) on a dense level, gather_generic.hip's on sparse points
 //   F2w = four bilinear taps of the first C channels of the target row (row stride C, or 3C with tgt_has_grad), x0+1 / y0+1
 //         clamped to W-1 / H-1 (utils_python.py:96-99), summed ((I00 w00 + I01 w01) + I10 w10) + I11 w11
 //   d_c = F2w_c - F1_c   (F1 = the source row; the sign does not reach the outputs)
@@ -54,7 +54,7 @@ struct ResGeo {
   bool m;
 };
 
-// sparse points: the geometry phase of ba_gather_kernel (gather.hip), statement for statement, without the Jacobians
+// sparse points: the geometry phase of ba_gather_kernel (gather_generic.hip), statement for statement, without the Jacobians
 __device__ __forceinline__ ResGeo sparse_geometry(const banet_level_t& lv, int b, const float (&Rm)[9], const float (&Tv)[3], bool valid,
                                                   int pt, float D) {
   const int N = lv.N, W = lv.W, H = lv.H;
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(kSumThreads) void ba_residual_sums_kernel(const flo
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// the shapes the assembly pass launches a gather for (gather.hip launch_c / launch_k; the C = 128 kernels take every K their plan
+// the shapes the assembly pass launches a gather for (plan.hpp: plan_gather_steps; the C = 128 kernels take every K their plan
 // admits): banet_ba_residual_f32 refuses the others with the assembly's code although its own kernel has no such limit
 int residual_shape_supported(const banet_level_t* lv) {
   if ((lv->C & 1) && lv->C > 128) return BANET_ERR_UNSUPPORTED;

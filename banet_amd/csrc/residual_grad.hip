@@ -4,7 +4,7 @@
 // forward's floor held fixed (the one-sided derivative at an integer coordinate, as banet_resample_grad_f32).  Per window b, target
 // frame f and point n, in this order:
 //   1. D = D0 + Bs.W, the ray, the projection, the mask and the four taps: the float32 statements of ba_residual_kernel
-//      (residual.hip) -- strip_geometry's (quad_common.hpp) on a dense level, gather.hip's on sparse points -- restated here
+//      (residual.hip) -- strip_geometry's (quad_common.hpp) on a dense level, gather_generic.hip's on sparse points -- restated here
 //      because the backward needs their intermediates (ray, R p, X / Z, Z);
 //   2. e_c = mask (2 gsq d_c + gab sgn d_c),  sgn 0 = 0;
 //   3. (dpx, dpy) = sum_c e_c dF2w_c / d(px, py) + mask gproj,  dF2w/dpx = (I01 - I00)(1 - dy) + (I11 - I10) dy, dF2w/dpy alike;
@@ -105,7 +105,7 @@ __device__ __forceinline__ RgRay dense_ray(const banet_level_t& lv, float fx0, f
   return r;
 }
 
-// sparse points: the loads of ba_gather_kernel's geometry phase (gather.hip)
+// sparse points: the loads of ba_gather_kernel's geometry phase (gather_generic.hip)
 __device__ __forceinline__ RgRay sparse_ray(const banet_level_t& lv, int b, bool valid, int pt, int cj) {
   const int N = lv.N;
   RgRay r;

@@ -671,7 +671,7 @@ def sparse_iteration_supported(conv1, conv2, Bs, D=None, R=None, T=None):
     """what the fused sparse node accepts (plan_adjoint, csrc/adjoint_plan.hpp): float32 CUDA tensors on ONE device, C <= 256, K <= 256, not C > 128 together
     with K > 128, a [f|gx|gy] map of at least 4 x 4 texels (the gather plans refuse smaller ones: the caller falls back to the lean
     torch graph instead of raising); no odd C or K above 128 -- the node's FORWARD is banet_ba_assemble_f32, whose generic gather kernel
-    is compiled for one channel / coefficient per lane up to 128 and two per lane up to 256 (csrc/gather.hip, launch_c / launch_k:
+    is compiled for one channel / coefficient per lane up to 128 and two per lane up to 256 (csrc/plan.hpp, plan_gather_steps:
     BANET_ERR_UNSUPPORTED otherwise), although the adjoint takes those shapes"""
     C = conv1.shape[-1]
     K = 0 if Bs is None else Bs.shape[-1]

@@ -84,7 +84,7 @@ NO_OUTSIDE_SHARE = {
     "empty-window": "window 1 is empty by construction (the other two are asserted)",
     "cluster-two-cells": "every point inside by construction",
 }
-# banet_ba_assemble_f32 has no kernel for these (csrc/gather.hip, launch_c / launch_k: the generic gather kernel is compiled for one
+# banet_ba_assemble_f32 has no kernel for these (csrc/plan.hpp, plan_gather_steps: the generic gather kernel is compiled for one
 # channel / coefficient per lane up to 128 and two per lane up to 256, so an odd C or K above 128 returns BANET_ERR_UNSUPPORTED): the
 # adjoint takes them, the forward test asserts the refusal and that dense_train.sparse_iteration_supported says so
 FORWARD_NOT_COMPILED = {"bundle-C7-K255": "odd K > 128", "camera-C131": "odd C > 128", "camera-C255": "odd C > 128"}

@@ -161,6 +161,18 @@ def _gather_axis():
     return out
 
 
+def _gather_fp_lds():
+    """the gather axis, continued: the frame-parallel strip workgroup on more than 64 KB of dynamic LDS, i.e. launched behind the
+    function attribute -- from 4 frames (78352 B) to 7 (136336 B); the slots of _gather_axis stop at 3 (59024 B).  Both scenes are the
+    SYRK axis's, so these cases stand behind it in the table: a scene goes by the name of its first case (all_scenes)."""
+    bits, sel, _ = gather_flag_sets()["strip"]
+    out = []
+    for (H, W), pairs in (((32, 48), 4), ((23, 21), 7)):
+        s, d, f = _syrk_sel(128, pairs)
+        out.append(_dense("gather_fp_strip_lds", H, W, 128, 128, pairs, bits, "large", sel, s, d, f))
+    return out
+
+
 def syrk_forms():
     """form -> [(tag, C, K, frames, flag bits, expected gather selection)]; the default gather: the 4x4-item kernel at C = 128 with
     K % 4 == 0 (latency-bound launches), the generic kernel otherwise"""
@@ -222,7 +234,7 @@ def _sparse_axis():
 
 @functools.lru_cache(maxsize=None)
 def all_cases():
-    cases = _gather_axis() + _syrk_axis() + _sparse_axis()
+    cases = _gather_axis() + _syrk_axis() + _gather_fp_lds() + _sparse_axis()
     assert len({c.name for c in cases}) == len(cases)
     return tuple(cases)
 

@@ -200,3 +200,111 @@ extern "C" void banet_test_syrk_stats(int f16, int f16_standalone, int it, int m
   out[0] = banet::syrk_stats_of_iteration(pl, it, max_iters);
   out[1] = banet::syrk_stats_of_single_pass(pl);
 }
+
+// ---- the gather step list (tests/test_gather_steps_cpu.py) --------------------------------------------------------------------------
+namespace {
+
+std::string gather_step_kernel(const banet::GatherStep& st) {
+  switch (st.kind) {
+    case banet::kGatherStepZero: return "zero_iters_kernel";
+    case banet::kGatherStepGeneric:
+      return fmt("ba_gather_kernel<%d, %d, ", st.t0, st.t1) + tf(st.t2) + fmt(", %d, %d>", st.t3, st.t4);
+    case banet::kGatherStepDirect: return fmt("ba_gather128_kernel<%d>", st.t0);
+    case banet::kGatherStepPatch: return fmt("ba_gather128p_kernel<%d, %d, ", st.t0, st.t1) + tf(st.t2) + ">";
+    case banet::kGatherStepStrip: return fmt("ba_gather128s_kernel<%d, %d, ", st.t0, st.t1) + tf(st.t2) + ">";
+    case banet::kGatherStepQuad: return fmt("ba_gather128q_kernel<%d>", st.t0);
+    case banet::kGatherStepFold: return "ba_fold_kernel";
+  }
+  return "?";
+}
+// "kernel[ words(n)] grid(x, y) block n lds n[ attr]": words = what the zeroing step clears
+std::string gather_step_line(const banet::GatherStep& st) {
+  return gather_step_kernel(st) + (st.kind == banet::kGatherStepZero ? fmt(" words(%d)", st.t0) : std::string()) +
+         fmt(" grid(%d, %d) block %d lds %d", st.gx, st.gy, st.block, st.lds) + (st.lds_attr ? " attr" : "");
+}
+
+struct LevelGatherSteps {
+  int rc_plan, rc;
+  banet::GatherSteps steps;
+};
+LevelGatherSteps level_gather_steps(const int32_t* desc, int cus, int reset_queue) {
+  banet_level_t lv = {};
+  lv.B = desc[0], lv.N = desc[1], lv.C = desc[2], lv.K = desc[3], lv.H = desc[4], lv.W = desc[5];
+  lv.dense = desc[6], lv.tgt_has_grad = desc[7], lv.pairs = desc[8], lv.policy = desc[9], lv.flags = desc[10];
+  lv.scale = 1.f;
+  LevelGatherSteps r = {};
+  banet::GatherPlan g;
+  r.rc_plan = r.rc = banet::plan_gather(&lv, cus, &g);
+  if (r.rc_plan == BANET_OK) r.rc = banet::plan_gather_steps(&lv, g, reset_queue != 0, &r.steps);
+  return r;
+}
+
+}  // namespace
+
+// one line per level of `desc` (rows as banet_test_plan_sweep's): "rc=<plan_gather_steps' code>" and then "; <step>" per launch, in
+// order.  Returns the bytes `text` needs (with its terminator).
+extern "C" size_t banet_test_gather_steps(const int32_t* desc, int n, int cus, int reset_queue, char* text, size_t cap) {
+  std::string all;
+  for (int i = 0; i < n; ++i, desc += kDescInts) {
+    const LevelGatherSteps r = level_gather_steps(desc, cus, reset_queue);
+    all += fmt("rc=%d", r.rc);
+    for (int k = 0; k < r.steps.n; ++k) all += "; " + gather_step_line(r.steps.step[k]);
+    all += "\n";
+  }
+  if (text && cap > all.size()) all.copy(text, all.size()), text[all.size()] = 0;
+  return all.size() + 1;
+}
+
+// the same over many levels without the text: out = (plan_gather's code, plan_gather_steps' code, steps) per level; returns the distinct
+// kernels the steps named, one per line
+extern "C" const char* banet_test_gather_steps_sweep(const int32_t* desc, int n, int cus, int reset_queue, int32_t* out) {
+  static std::string s;
+  std::set<std::string> seen;
+  for (int i = 0; i < n; ++i, desc += kDescInts) {
+    const LevelGatherSteps r = level_gather_steps(desc, cus, reset_queue);
+    *out++ = r.rc_plan, *out++ = r.rc, *out++ = r.steps.n;
+    for (int k = 0; k < r.steps.n; ++k) seen.insert(gather_step_kernel(r.steps.step[k]));
+  }
+  s.clear();
+  for (const std::string& k : seen) s += k + "\n";
+  return s.c_str();
+}
+
+extern "C" int banet_test_gather_max_steps() { return banet::kGatherMaxSteps; }
+
+// every instantiation of the X-macro lists, one per line
+extern "C" const char* banet_test_gather_instantiations() {
+  static std::string s;
+  s.clear();
+#define X(vec, ch, grad, kvec, kch) s += "ba_gather_kernel<" #vec ", " #ch ", " #grad ", " #kvec ", " #kch ">\n";
+  BANET_GATHER_GENERIC_LIST(X)
+#undef X
+#define X(kv4) s += "ba_gather128_kernel<" #kv4 ">\n";
+  BANET_GATHER_DIRECT_LIST(X)
+#undef X
+#define X(kv4, us, fs) s += "ba_gather128p_kernel<" #kv4 ", " #us ", " #fs ">\n";
+  BANET_GATHER_PATCH_LIST(X)
+#undef X
+#define X(kv4, nch, fp) s += "ba_gather128s_kernel<" #kv4 ", " #nch ", " #fp ">\n";
+  BANET_GATHER_STRIP_LIST(X)
+#undef X
+#define X(kv4) s += "ba_gather128q_kernel<" #kv4 ">\n";
+  BANET_GATHER_QUAD_LIST(X)
+#undef X
+  return s.c_str();
+}
+
+// plan_gather_steps on a hand-made plan (what plan_gather never produces): desc = one level row, then strip, strip_fp; returns its code
+extern "C" int banet_test_gather_steps_of_strip(const int32_t* desc, int strip, int strip_fp) {
+  banet_level_t lv = {};
+  lv.B = desc[0], lv.N = desc[1], lv.C = desc[2], lv.K = desc[3], lv.H = desc[4], lv.W = desc[5];
+  lv.dense = desc[6], lv.tgt_has_grad = desc[7], lv.pairs = desc[8], lv.policy = desc[9], lv.flags = desc[10];
+  banet::GatherPlan g = {};
+  g.c128 = 1, g.G = 1, g.strip = strip, g.strip_fp = strip_fp;
+  banet::GatherSteps steps;
+  const int rc = banet::plan_gather_steps(&lv, g, false, &steps);
+  return rc != BANET_OK && steps.n != 0 ? 1 : rc;
+}
+
+// the dynamic LDS of a frame-parallel strip workgroup
+extern "C" size_t banet_test_strip_fp_lds_bytes(int pairs, int nch) { return banet::strip_fp_lds_bytes(pairs, nch); }

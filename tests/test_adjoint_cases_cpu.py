@@ -96,7 +96,7 @@ def test_cases_are_reproducible_and_cover_the_listed_shapes():
     for n_ in ac.ACCUMULATION_CASES + (ac.REPRODUCIBILITY_CASE,):
         assert n_ in ac.BY_NAME
     assert all(c.N <= 4096 for c in ac.CASES)
-    # the forward has a kernel for every case but those with an odd C or K above 128 (gather.hip, launch_c / launch_k)
+    # the forward has a kernel for every case but those with an odd C or K above 128 (plan.hpp, plan_gather_steps)
     assert set(ac.FORWARD_NOT_COMPILED) == {c.name for c in ac.CASES if (c.C > 128 and c.C % 2) or (c.K > 128 and c.K % 2)}
 
 

@@ -82,8 +82,13 @@ RangeScope::~RangeScope() {
 int profile_begin(int max_launches) {
   if (g_prof.on || max_launches <= 0) return BANET_ERR_INVALID_ARG;
   g_prof.ev.resize((size_t)2 * max_launches);
+  // timing-only events: nothing on the host reads device memory behind them, so they do without the system-scope acquire / release
+  // (cache write-back and invalidation) a default event puts around every bracketed launch.  BANET_PROFILE_EVENT_FENCE=1: default
+  // events (A/B of the profiled step; unprofiled runs record no events either way)
+  const char* fence = std::getenv("BANET_PROFILE_EVENT_FENCE");
+  const unsigned flags = (fence && fence[0] == '1') ? hipEventDefault : hipEventDisableSystemFence;
   for (auto& e : g_prof.ev)
-    if (hipEventCreate(&e) != hipSuccess) return BANET_ERR_LAUNCH;
+    if (hipEventCreateWithFlags(&e, flags) != hipSuccess) return BANET_ERR_LAUNCH;
   g_prof.tag.assign(max_launches, 0);
   g_prof.used = 0;
   g_prof.on = true;

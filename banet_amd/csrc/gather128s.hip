@@ -408,14 +408,8 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
         DYv[hh][c4] = ge.dy;
         // min / max of (x0, y0) over the 16 fast pixels of this lane's pixel row (lanes that agree in lane & 3)
         const int big = 0x3fffffff;
-        int ymn = fast ? ge.y0 : big, ymx = fast ? ge.y0 : -big, xmn = fast ? ge.x0 : big, xmx = fast ? ge.x0 : -big;
-#pragma unroll
-        for (int sh = 4; sh < 64; sh <<= 1) {
-          ymn = min(ymn, __shfl_xor(ymn, sh, 64));
-          ymx = max(ymx, __shfl_xor(ymx, sh, 64));
-          xmn = min(xmn, __shfl_xor(xmn, sh, 64));
-          xmx = max(xmx, __shfl_xor(xmx, sh, 64));
-        }
+        const int ymn = wave_minmax<false, true>(fast ? ge.y0 : big), ymx = wave_minmax<true, true>(fast ? ge.y0 : -big);
+        const int xmn = wave_minmax<false, true>(fast ? ge.x0 : big), xmx = wave_minmax<true, true>(fast ? ge.x0 : -big);
         if (lane < 4) {
           StripRowStat st;
           st.ymin = ymn;
@@ -431,22 +425,15 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
       {
         StripRowStat st = sStat[lane & (SEGH - 1)];
         if (lane >= SEGH) st.ymin = 1, st.ymax = 0;                    // lanes SEGH..63: no row
-        int xm = st.ymin <= st.ymax ? st.xmin : 0x3fffffff;
-#pragma unroll
-        for (int sh = 1; sh < 64; sh <<= 1) xm = min(xm, __shfl_xor(xm, sh, 64));
+        const int xm = wave_minmax<false, false>(st.ymin <= st.ymax ? st.xmin : 0x3fffffff);
         xl = rfl(strip_window_origin(xm, W));
         StripLaneEnv env;
         env.modev = strip_static_mode(st, xl, W);
         env.ytv = st.ymin - 1;
         env.ybv = st.ymax + 2;
         env.ctlv = env.yfv = env.ringv = 0;
-        int ye = env.modev == kStepWindow ? env.ybv : -0x3fffffff;
-        int xe = env.modev == kStepWindow ? st.xmax + 2 - xl : 0;      // last window column any row served from the window reads
-#pragma unroll
-        for (int sh = 1; sh < 64; sh <<= 1) {
-          ye = max(ye, __shfl_xor(ye, sh, 64));
-          xe = max(xe, __shfl_xor(xe, sh, 64));
-        }
+        const int ye = wave_minmax<true, false>(env.modev == kStepWindow ? env.ybv : -0x3fffffff);
+        const int xe = wave_minmax<true, false>(env.modev == kStepWindow ? st.xmax + 2 - xl : 0);      // last window column any row served from the window reads
         // lanes of the third LDS-DMA instruction of a window row (texels 16 .. xe, 8 lanes each): the 21-texel pitch is the
         // capacity, a unit-scale segment reads 19 or 20 of them -- the rest is not fetched.  At least one texel: the plan
         // counts kRowOps = 3 operations per row, and an instruction whose lanes are all off is branched around.
@@ -661,12 +648,7 @@ __global__ __launch_bounds__(FP ? 512 : kSBlock, 2) __attribute__((amdgpu_num_vg
         // columns (fixed order); lanes 0..3 publish
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float lo = hA ? absB[e] : absA[e], hi = hA ? absA[e] : absB[e];
-#pragma unroll
-          for (int sh = 4; sh < 64; sh <<= 1) {
-            lo += __shfl_xor(lo, sh, 64);
-            hi += __shfl_xor(hi, sh, 64);
-          }
+          const float lo = cols16_sum_lanes03(hA ? absB[e] : absA[e]), hi = cols16_sum_lanes03(hA ? absA[e] : absB[e]);
           if (lane < 4) {
             sScrW[32 * s + 4 * oc + e] = lo;
             sScrW[32 * s + 16 + 4 * oc + e] = hi;

@@ -28,6 +28,44 @@ __device__ __forceinline__ float quad_bcast(float v) {
   return __builtin_bit_cast(float, quad_bcast<K4>(__builtin_bit_cast(int, v)));
 }
 
+// ---- reductions of the lane = pixel phases on DPP + the half / row swaps: no ds_bpermute (__shfl_xor), no s_waitcnt lgkmcnt ----
+constexpr int kDppShl4 = 0x104;        // lane i <- lane i + 4 of its 16-lane row (lanes 12..15 read nothing: 0 with bound_ctrl)
+constexpr int kDppRor4 = 0x124;        // lane i <- the lane 4 away around its 16-lane row
+template <int CTRL>
+__device__ __forceinline__ int dpp_movi(int v) {
+  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false);
+}
+// min (MAX = false) / max over the wave; COLS: over the 16 lanes that agree in lane & 3 only (one pixel row of a chunk: lane = 4 x
+// column + row).  Every lane gets the result; exact, so the order does not matter.
+template <bool MAX, bool COLS>
+__device__ __forceinline__ int wave_minmax(int v) {
+  auto op = [](int a, int b) { return MAX ? max(a, b) : min(a, b); };
+  if constexpr (COLS) {
+    v = op(v, dpp_movi<kDppRor4>(v));
+    v = op(v, dpp_movi<kDppRor8>(v));
+  } else {
+    v = op(v, dpp_movi<kDppRor8>(v));
+    v = op(v, dpp_movi<kDppHalfMirror>(v));
+    v = op(v, dpp_movi<kDppXor2>(v));
+    v = op(v, dpp_movi<kDppXor1>(v));
+  }
+  int a = v, b = v;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));   // (s_nop: VALU write -> permlane read, cf. bfly_merge)
+  v = op(a, b);
+  a = v;
+  b = v;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return op(a, b);
+}
+// sum over the 16 lanes that agree in lane & 3, valid on LANES 0..3 only, in the pairing of the xor butterfly over the lane
+// distances 4, 8, 16, 32 ((v[l] + v[l+4]) + (v[l+8] + v[l+12]) per row, rows 0 + 1 and 2 + 3, then the halves): the same bits
+__device__ __forceinline__ float cols16_sum_lanes03(float v) {
+  v += dpp_mov<kDppShl4>(v);
+  v += dpp_mov<kDppRor8>(v);
+  v = bfly_merge(v, v, 16);
+  return bfly_merge(v, v, 32);
+}
+
 struct SGeo {
   float dx, dy, jd0, jd1;
   float jc[12];

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Read the BANET_TIMING cycle counters of the strip gather (ba_gather128s_kernel; build with
-EXTRA_HIPCC_FLAGS=-DBANET_TIMING=1 or =2 into banet_amd/lib_timing{1,2}): where does a 16x32 segment spend its cycles?"""
+EXTRA_HIPCC_FLAGS=-DBANET_TIMING=1 or =2 into banet_amd/lib_timing{1,2}): where does a segment spend its cycles?
+PB windows of PW x PH (default 32 of 640 x 480), PK coefficients, PP target frames, PMODE = the build's BANET_TIMING, PSEGH rows per segment."""
 import ctypes
 import os
 import sys
@@ -11,7 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from banet_amd import _capi as capi, dense as bdense, ops, synth as bsynth  # noqa: E402
 from banet_amd.bundlenet import he_normal_lambda_weights  # noqa: E402
 
-B, H, W, C, K = int(os.environ.get("PB", "32")), 480, 640, 128, int(os.environ.get("PK", "128"))
+B, H, W, C, K = int(os.environ.get("PB", "32")), int(os.environ.get("PH", "480")), int(os.environ.get("PW", "640")), 128, int(os.environ.get("PK", "128"))
 MODE = int(os.environ.get("PMODE", "1"))
 PP = int(os.environ.get("PP", "1"))     # target frames per window (frame-parallel workgroups when > 1)
 dev = torch.device("cuda:0")

@@ -164,6 +164,18 @@ class Prior(ctypes.Structure):
                 ("reserved_", ctypes.c_int32)]
 
 
+class PriorGradIn(ctypes.Structure):
+    """mirror of banet_prior_grad_in_t (banet_prior_terms_grad_f32: gLe / gee required, Le / ee for gscale, reserved_ = 0)"""
+    _fields_ = [("gLe", _FP), ("gee", _FP), ("Le", _FP), ("ee", _FP), ("flags", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+
+
+class PriorGradOut(ctypes.Structure):
+    """mirror of banet_prior_grad_out_t (every pointer optional)"""
+    _fields_ = [("gLambda", _FP), ("geta", _FP), ("gscale", _FP), ("gobs", _FP), ("gweight", _FP), ("gdepth", _FP), ("gbasis", _FP)]
+
+
+PRIOR_GRAD_OVERWRITE, PRIOR_GRAD_ACCUMULATE = 1, 2  # banet_hip.h: BANET_PRIOR_GRAD_OVERWRITE / _ACCUMULATE
+
 ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2  # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
 
 EXPORTS = {
@@ -223,6 +235,11 @@ EXPORTS = {
                                                 ctypes.c_size_t, _FP]),
     "banet_lm_solve_prior_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Schedule), ctypes.POINTER(Prior)]),
     "banet_lm_solve_prior_f32": (ctypes.c_int, [ctypes.POINTER(Schedule), ctypes.POINTER(Prior), ctypes.POINTER(State), _FP]),
+    "banet_prior_terms_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Prior)] + [_FP] * 2 + [_FP, ctypes.c_size_t, _FP]),
+    "banet_prior_add_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level)] + [_FP] * 7 + [ctypes.c_int, _FP]),
+    "banet_prior_terms_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.POINTER(Prior)]),
+    "banet_prior_terms_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Prior), ctypes.POINTER(PriorGradIn),
+                                                  ctypes.POINTER(PriorGradOut), _FP, ctypes.c_size_t, _FP]),
     "banet_sample_stats_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "banet_sample_stats_grad_det_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 5 + [_FP] * 5 + [_FP, ctypes.c_size_t, _FP]),
     "banet_spd_solve_f32": (ctypes.c_int, [_FP] * 3 + [ctypes.c_int] * 2 + [_FP]),

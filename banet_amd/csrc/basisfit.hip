@@ -132,7 +132,7 @@ __device__ __forceinline__ void fit_gram_wave(const FitArgs& a, int b, int n0, i
   for (int nb = n0; nb < n1; nb += 2 * kFitBatch) {
     load_batch(nb + 2 * kFitBatch, nxt);   // (past the range on the last round: the clamped pixel again, never consumed)
     // the lane's own pixel of the batch: does it contribute?  (NaN fails each comparison)
-    const bool mine = (nb + (lane & 7) < n1) && (cur.w > 0.f) && (cur.w < __builtin_huge_valf()) && (fabsf(cur.t) < __builtin_huge_valf());
+    const bool mine = (nb + (lane & 7) < n1) && fit_point_counted(cur.w, cur.t);
     const float wl = mine ? cur.w : 0.f, rl = mine ? cur.t - cur.d : 0.f;
 #pragma unroll
     for (int u = 0; u < kFitBatch; ++u) {

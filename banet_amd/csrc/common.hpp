@@ -24,6 +24,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Does a point with weight w and observation / target t enter a weighted depth fit -- banet_basis_fit_f32, the prior's observation
+// half and its backward?  A finite w > 0 and a finite t (NaN fails each comparison).  One statement for all of them.
+__device__ __forceinline__ bool fit_point_counted(float w, float t) {
+  return (w > 0.f) && (w < __builtin_huge_valf()) && (fabsf(t) < __builtin_huge_valf());
+}
+
 // ---- cross-lane primitives (wave64, gfx950) ------------------------------------------------
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {  // CTRL: LLVM dpp_ctrl encoding

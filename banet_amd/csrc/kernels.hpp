@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "grid_plan.hpp"   // the grid resampler's geometry (host-only like plan.hpp)
 #include "prior_plan.hpp"  // the prior term's regions and the Gram pass's partial rows (host-only like plan.hpp)
+#include "prior_grad_plan.hpp"  // its backward: outputs, per-pixel grid, Gh / gh regions (host-only like plan.hpp)
 
 namespace banet {
 

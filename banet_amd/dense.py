@@ -215,14 +215,17 @@ class DenseBA:
                 depth_outputs.append(ops.depth_output(prob.keep[2], prob.keep[3], st.Wc).reshape(self.levels[li].depth.shape))
         return st, counts
 
-    def solve_differentiable(self, iters_per_level, R=None, T=None, Wc=None, outputs=None):
+    def solve_differentiable(self, iters_per_level, R=None, T=None, Wc=None, outputs=None, prior=None):
         """The same fixed-count schedule attached to the autograd graph: gradients flow to the levels' src / tgt / depth /
         basis tensors, to the initial (R, T, Wc) and to the lambda weights through the fused backward kernels
         (banet_amd/dense_train.py, csrc/adjoint.hip; the reference differentiates bundlenet.py:376-397 with tf.gradients +
         EquationConstructionGrad).  `bundle` (K <= 256) and the pose-only `bundle_camera` variant; two-frame and multi-frame
-        windows.  outputs: a list that receives (R, T, Wc) after each level, attached to the graph."""
+        windows.  outputs: a list that receives (R, T, Wc) after each level, attached to the graph.  prior: a DensePrior as in
+        solve(prior=) (`bundle` only, K >= 1); its tensors may require grad -- a learned obs_depth / obs_weight, the (Lambda, eta) of
+        transfer_prior -- and the levels' depth and basis receive the term's gradient as well.  None or empty: today's launches."""
         from . import dense_train
-        return dense_train.solve_differentiable(self, self.levels, self.lambda_weights, iters_per_level, R, T, Wc, outputs=outputs)
+        return dense_train.solve_differentiable(self, self.levels, self.lambda_weights, iters_per_level, R, T, Wc, outputs=outputs,
+                                                prior=prior)
 
     def step_from(self, level_index, R, T, Wc=None):
         """ONE iteration of level `level_index` from the given state -> (state after it; .delta / .lambda_out hold the

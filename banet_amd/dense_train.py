@@ -385,79 +385,133 @@ class _LevelSolve(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gR, gT, gW):
-        ba, li = ctx.ba, ctx.li
-        prob = ba.problems[li]
-        pairs = prob.pairs
-        dev = prob.device
-        camera = ba.variant == "bundle_camera"
-        B, N, C, K, H, W = prob.B, prob.N, prob.C, prob.K, prob.c.H, prob.c.W
-        pprobs = [prob] if pairs == 1 else _pair_problems(ba, li)
-        # no zero-fills: the first adjoint call that touches a buffer writes it (BANET_ADJOINT_OVERWRITE), the later ones accumulate --
-        # 25 GB of fills and as many bytes of reads per 32-window 640x480 level
-        # the target gradient per texel tile: no 3C rows, no [f|gx|gy] map adjoint, no fold pass -- where the library takes the level
-        # in that mode (dense layout, a window's maps below 4 GB: the tile kernels use 32-bit byte offsets); else the round-5 path
-        fold = FOLD_MODE != "0" and capi.lib().banet_dense_adjoint_workspace_bytes_ex(ctypes.byref(pprobs[0].c), ADJOINT_FOLD_TARGET) != 0
-        xflags = ADJOINT_TILE_SHAPE(TILE_SHAPE)
-        dsrc = torch.empty((B, N, C), dtype=torch.float32, device=dev)
-        dmap3 = [torch.empty((B, H, W, C if fold else 3 * C), dtype=torch.float32, device=dev) for _ in range(pairs)]
-        ddepth = torch.empty((B, N), dtype=torch.float32, device=dev)
-        dbasis = torch.empty((B, N, K), dtype=torch.float32, device=dev)
-        flat = ctx.layers
-        gR = torch.zeros(B, pairs, 3, 3, device=dev) if gR is None else gR.reshape(B, pairs, 3, 3)
-        gT = torch.zeros(B, pairs, 3, 1, device=dev) if gT is None else gT.reshape(B, pairs, 3, 1)
-        gW = torch.zeros(B, K, 1, device=dev) if gW is None else gW.reshape(B, K, 1)
-        o = 6 * pairs
-        ws = None
-        first = True
-        if not ctx.saved:                                  # (no iteration ran: nothing writes the buffers)
-            for t in [dsrc, ddepth, dbasis] + dmap3:
-                t.zero_()
-        hip_small = SmallStepHip(ba.variant, B, N, C, K, pairs, ctx.mlp, ba.l2_base, dev) \
-            if SmallStepHip.supported(ba.variant, B, N, C, K, pairs, dev) else None
-        glayers = None if hip_small is not None else [torch.zeros_like(t) for t in flat]
-        for Ri, Ti, Wi, AtA, Atb, absres, delta in reversed(ctx.saved):
-            Rv, Tv = Ri.reshape(B, pairs, 3, 3), Ti.reshape(B, pairs, 3, 1)
-            if hip_small is not None:       # four launches; the lambda-weight gradients accumulate on the device
-                gAtA, gAtb, gabs, dR, dT = hip_small(AtA, Atb, absres, delta, Rv, Tv, gR, gT, gW)
-                gR, gT = dR, dT             # (gW: W' = W + sol, the upstream gradient passes through)
-                gW = gW.clone()
-            else:
-                grads = _small_step([AtA, Atb, absres, Rv, Tv, Wi, gR, gT, gW] + [t.detach() for t in flat], N, ba.l2_base, pairs, camera)
-                gAtA, gAtb, gabs, dR, dT, dW = grads[:6]
-                for acc, g in zip(glayers, grads[6:]):
-                    acc += g
-                gR, gT, gW = dR.reshape(B, pairs, 3, 3).clone(), dT.reshape(B, pairs, 3, 1).clone(), dW.reshape(B, K, 1).clone()
-            for i in range(pairs):
-                if pairs == 1:
-                    gA_i, gb_i = gAtA, gAtb
-                else:       # E_i^T (dL/dAtA) E_i: the frame's pose block, its cross blocks with the depth block, the depth block
-                    idx = torch.cat([torch.arange(6 * i, 6 * i + 6, device=dev), torch.arange(o, o + K, device=dev)])
-                    gA_i = gAtA.index_select(1, idx).index_select(2, idx).contiguous()
-                    gb_i = gAtb.index_select(1, idx).contiguous()
-                # dmap3[i] is fresh for every frame of the first iteration; dsrc / ddepth / dbasis are shared by the frames
-                dpose, ws = dense_adjoint(pprobs[i], Rv[:, i].contiguous(), Tv[:, i].contiguous(), Wi, gA_i, gb_i, gabs, dsrc,
-                                          dmap3[i], ddepth, dbasis, ws, overwrite=first and i == 0, overwrite_map=first, fold=fold,
-                                          extra_flags=xflags | (ADJOINT_REUSE_DEPTH_SEED if (i > 0 and REUSE_MODE != "0") else 0))
-                gR[:, i] += dpose[:, 0:9].reshape(B, 3, 3)
-                gT[:, i] += dpose[:, 9:12].reshape(B, 3, 1)
-                gW += dpose[:, 12:].reshape(B, K, 1)
-            first = False
-        if fold:                                           # dmap3[i] IS the frame's target gradient
-            dtgt = dmap3[0].view(B, 1, H, W, C) if pairs == 1 else torch.stack(dmap3, 1)
-        elif pairs == 1:                                   # written in place: no fill, no copy
-            dtgt = torch.empty((B, 1, H, W, C), dtype=torch.float32, device=dev)
-            target_map_adjoint(dmap3[0], dtgt.view(B, H, W, C), overwrite=True)
+        return (None, None, None) + _level_backward(ctx, gR, gT, gW)
+
+
+def _level_backward(ctx, gR, gT, gW, prior=None, Le=None, prior_want=()):
+    """The backward of a level's iterations -> (dsrc, dtgt, ddepth, dbasis, gR, gT, gW, *glayers), and with a prior (the level's
+    ops.Prior, its terms Le, the prior outputs some input needs) the ops.PriorGrad behind them.  Without one: _LevelSolve's launches."""
+    ba, li = ctx.ba, ctx.li
+    prob = ba.problems[li]
+    pairs = prob.pairs
+    dev = prob.device
+    camera = ba.variant == "bundle_camera"
+    B, N, C, K, H, W = prob.B, prob.N, prob.C, prob.K, prob.c.H, prob.c.W
+    pprobs = [prob] if pairs == 1 else _pair_problems(ba, li)
+    # no zero-fills: the first adjoint call that touches a buffer writes it (BANET_ADJOINT_OVERWRITE), the later ones accumulate --
+    # 25 GB of fills and as many bytes of reads per 32-window 640x480 level
+    # the target gradient per texel tile: no 3C rows, no [f|gx|gy] map adjoint, no fold pass -- where the library takes the level
+    # in that mode (dense layout, a window's maps below 4 GB: the tile kernels use 32-bit byte offsets); else the round-5 path
+    fold = FOLD_MODE != "0" and capi.lib().banet_dense_adjoint_workspace_bytes_ex(ctypes.byref(pprobs[0].c), ADJOINT_FOLD_TARGET) != 0
+    xflags = ADJOINT_TILE_SHAPE(TILE_SHAPE)
+    dsrc = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+    dmap3 = [torch.empty((B, H, W, C if fold else 3 * C), dtype=torch.float32, device=dev) for _ in range(pairs)]
+    ddepth = torch.empty((B, N), dtype=torch.float32, device=dev)
+    dbasis = torch.empty((B, N, K), dtype=torch.float32, device=dev)
+    flat = ctx.layers
+    gR = torch.zeros(B, pairs, 3, 3, device=dev) if gR is None else gR.reshape(B, pairs, 3, 3)
+    gT = torch.zeros(B, pairs, 3, 1, device=dev) if gT is None else gT.reshape(B, pairs, 3, 1)
+    gW = torch.zeros(B, K, 1, device=dev) if gW is None else gW.reshape(B, K, 1)
+    o = 6 * pairs
+    ws = None
+    first = True
+    if not ctx.saved:                                  # (no iteration ran: nothing writes the buffers)
+        for t in [dsrc, ddepth, dbasis] + dmap3:
+            t.zero_()
+    hip_small = SmallStepHip(ba.variant, B, N, C, K, pairs, ctx.mlp, ba.l2_base, dev) \
+        if SmallStepHip.supported(ba.variant, B, N, C, K, pairs, dev) else None
+    glayers = None if hip_small is not None else [torch.zeros_like(t) for t in flat]
+    gLe = gee = None
+    for Ri, Ti, Wi, AtA, Atb, absres, delta in reversed(ctx.saved):
+        Rv, Tv = Ri.reshape(B, pairs, 3, 3), Ti.reshape(B, pairs, 3, 1)
+        if hip_small is not None:       # four launches; the lambda-weight gradients accumulate on the device
+            gAtA, gAtb, gabs, dR, dT = hip_small(AtA, Atb, absres, delta, Rv, Tv, gR, gT, gW)
+            gR, gT = dR, dT             # (gW: W' = W + sol, the upstream gradient passes through)
+            gW = gW.clone()
         else:
-            dtgt = torch.empty((B, pairs, H, W, C), dtype=torch.float32, device=dev)
-            for i in range(pairs):
-                di = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-                target_map_adjoint(dmap3[i], di, overwrite=True)
-                dtgt[:, i] = di
-        if hip_small is not None:
-            glayers = [g.reshape(t.shape) for g, t in zip(hip_small.glayers, flat)]
-        s_src, s_tgt, s_dep, s_bas, s_R, s_T = ctx.shapes
-        return (None, None, None, dsrc.reshape(s_src), dtgt.reshape(s_tgt), ddepth.reshape(s_dep),
-                None if s_bas is None else dbasis.reshape(s_bas), gR.reshape(s_R), gT.reshape(s_T), gW) + tuple(glayers)
+            grads = _small_step([AtA, Atb, absres, Rv, Tv, Wi, gR, gT, gW] + [t.detach() for t in flat], N, ba.l2_base, pairs, camera)
+            gAtA, gAtb, gabs, dR, dT, dW = grads[:6]
+            for acc, g in zip(glayers, grads[6:]):
+                acc += g
+            gR, gT, gW = dR.reshape(B, pairs, 3, 3).clone(), dT.reshape(B, pairs, 3, 1).clone(), dW.reshape(B, K, 1).clone()
+        if prior is not None:       # gAtA / gAtb are the post-prior matrices' and pass through; gLe / gee accumulate, gW -= Le^T gAtb
+            gLe, gee, _ = ops.prior_add_grad(prob, Le, Wi, capi.f32c(gAtA), capi.f32c(gAtb), gLe, gee, gWc=gW.view(B, K))
+        for i in range(pairs):
+            if pairs == 1:
+                gA_i, gb_i = gAtA, gAtb
+            else:       # E_i^T (dL/dAtA) E_i: the frame's pose block, its cross blocks with the depth block, the depth block
+                idx = torch.cat([torch.arange(6 * i, 6 * i + 6, device=dev), torch.arange(o, o + K, device=dev)])
+                gA_i = gAtA.index_select(1, idx).index_select(2, idx).contiguous()
+                gb_i = gAtb.index_select(1, idx).contiguous()
+            # dmap3[i] is fresh for every frame of the first iteration; dsrc / ddepth / dbasis are shared by the frames
+            dpose, ws = dense_adjoint(pprobs[i], Rv[:, i].contiguous(), Tv[:, i].contiguous(), Wi, gA_i, gb_i, gabs, dsrc,
+                                      dmap3[i], ddepth, dbasis, ws, overwrite=first and i == 0, overwrite_map=first, fold=fold,
+                                      extra_flags=xflags | (ADJOINT_REUSE_DEPTH_SEED if (i > 0 and REUSE_MODE != "0") else 0))
+            gR[:, i] += dpose[:, 0:9].reshape(B, 3, 3)
+            gT[:, i] += dpose[:, 9:12].reshape(B, 3, 1)
+            gW += dpose[:, 12:].reshape(B, K, 1)
+        first = False
+    if fold:                                           # dmap3[i] IS the frame's target gradient
+        dtgt = dmap3[0].view(B, 1, H, W, C) if pairs == 1 else torch.stack(dmap3, 1)
+    elif pairs == 1:                                   # written in place: no fill, no copy
+        dtgt = torch.empty((B, 1, H, W, C), dtype=torch.float32, device=dev)
+        target_map_adjoint(dmap3[0], dtgt.view(B, H, W, C), overwrite=True)
+    else:
+        dtgt = torch.empty((B, pairs, H, W, C), dtype=torch.float32, device=dev)
+        for i in range(pairs):
+            di = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+            target_map_adjoint(dmap3[i], di, overwrite=True)
+            dtgt[:, i] = di
+    if hip_small is not None:
+        glayers = [g.reshape(t.shape) for g, t in zip(hip_small.glayers, flat)]
+    pg = None
+    if prior is not None and gLe is not None:          # once per level: the term adds into the dense adjoint's ddepth / dbasis
+        want = tuple(prior_want) + (("gdepth", "gbasis") if prior.obs_depth is not None else ())
+        if want:
+            pg = ops.prior_terms_grad(prob, prior, gLe, gee, want=want, accumulate=True, into=dict(gdepth=ddepth, gbasis=dbasis))
+    s_src, s_tgt, s_dep, s_bas, s_R, s_T = ctx.shapes
+    res = (dsrc.reshape(s_src), dtgt.reshape(s_tgt), ddepth.reshape(s_dep),
+           None if s_bas is None else dbasis.reshape(s_bas), gR.reshape(s_R), gT.reshape(s_T), gW) + tuple(glayers)
+    return res if prior is None else (res, pg)
+
+
+class _LevelSolvePrior(torch.autograd.Function):
+    """All fixed-count iterations of one pyramid level with an ops.Prior: its terms are formed once (banet_prior_terms_f32) and
+    applied between assembly and solve of every iteration as Prior(Le, ee, scale=1) -- the bits of ops.lm_level(prior=) -- and the
+    POST-prior AtA / Atb are what the small step's backward is given (the damping sees the prior on the diagonal).  The prior's
+    tensors enter as inputs so that autograd sees them; Lambda / eta, shared by the levels, sum over them there."""
+
+    @staticmethod
+    def forward(ctx, ba, li, n_iter, prior, src, tgt, depth, basis, R, T, Wc, Lambda, eta, obs, weight, *flat_layers):
+        prob, mlp = ba.problems[li], ba.mlps[li]
+        pairs = prob.pairs
+        st = ops.LmState(R.detach(), T.detach(), Wc.detach(), P=6 * pairs + ba.K, pairs=pairs)
+        Le, ee = ops.prior_terms(prob, prior)
+        unit = ops.Prior(Lambda=Le, eta=ee, scale=1.0)
+        saved = []
+        sws = pws = None
+        for _ in range(n_iter):
+            Ri, Ti, Wi = st.R.clone(), st.T.clone(), st.Wc.clone()
+            AtA, Atb, absres, nvalid = ops.ba_assemble(prob, st.R, st.T, st.Wc)
+            pws = ops.prior_apply(prob, unit, st.Wc, AtA, Atb, pws)
+            sws = ops.ba_solve_update(prob, mlp, ba.l2_base, AtA, Atb, absres, nvalid, st, sws)
+            saved.append((Ri, Ti, Wi, AtA, Atb, absres, st.delta.clone()))
+        ctx.ba, ctx.li, ctx.saved = ba, li, saved
+        ctx.mlp = mlp
+        ctx.layers = flat_layers
+        ctx.prior, ctx.Le = prior, Le
+        ctx.shapes = (src.shape, tgt.shape, depth.shape, None if basis is None else basis.shape, R.shape, T.shape)
+        ctx.pshapes = [None if x is None else x.shape for x in (Lambda, eta, obs, weight)]
+        return st.R.clone().reshape(R.shape), st.T.clone().reshape(T.shape), st.Wc.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gR, gT, gW):
+        names = ("gLambda", "geta", "gobs", "gweight")
+        want = tuple(n for n, k, s in zip(names, ctx.needs_input_grad[11:15], ctx.pshapes) if k and s is not None)
+        res, pg = _level_backward(ctx, gR, gT, gW, ctx.prior, ctx.Le, want)
+        gp = [None if (pg is None or n not in want) else getattr(pg, n).reshape(s) for n, s in zip(names, ctx.pshapes)]
+        return (None, None, None, None) + res[:7] + tuple(gp) + res[7:]
 
 
 class _AssembleDiff(torch.autograd.Function):
@@ -557,15 +611,27 @@ def depth_nll_loss(depth, depth_var, depth_gt, mask=None, var_floor=1e-12):
     return torch.where(keep, nll, torch.zeros_like(nll)).sum(1) / keep.sum(1).clamp(min=1)
 
 
-def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=None, Wc=None, outputs=None):
+def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=None, Wc=None, outputs=None, prior=None):
     """Differentiable DenseBA.solve with fixed iteration counts: `levels` = the DenseLevel objects `ba` was built from (their
     src / tgt / depth / basis tensors may require grad), `lambda_weights` = per level five (filters, biases) pairs (tensors
     that may require grad, or arrays).  Returns (R [B,3,3], T [B,3,1], Wc [B,K,1]) attached to the autograd graph
     (multi-frame windows: R [B,pairs,3,3], T [B,pairs,3,1]; the pose-only `bundle_camera` variant: K = 0, Wc is empty).
     outputs: a list that receives (R, T, Wc) after each level, attached to the graph (the per-level outputs of
-    bundlenet.py:376-399; a level with no iterations repeats the state it was given)."""
+    bundlenet.py:376-399; a level with no iterations repeats the state it was given).
+    prior: a dense.DensePrior whose tensors may require grad (coef = (Lambda, eta), each level's obs / weight): its term is added
+    between assembly and solve of every iteration as DenseBA.solve(prior=) adds it, and gradients reach the prior's tensors, and
+    through the term the levels' depth and basis (banet_prior_add_grad_f32 / banet_prior_terms_grad_f32).  `bundle` only, K >= 1.
+    None or an empty prior: the launches and bits of the call without the argument."""
     if ba.variant not in ("bundle", "bundle_camera"):
         raise capi.BanetError("solve_differentiable: bundle / bundle_camera variants only")
+    priors = None
+    if prior is not None:
+        if ba.variant != "bundle" or ba.K < 1:
+            raise capi.BanetError("solve_differentiable: a prior needs the `bundle` variant with K >= 1")
+        n = min(len(ba.problems), len(iters_per_level))
+        priors = prior.level_priors(ba.problems[:n])
+        if any(ops.prior_workspace_bytes(p, q) == 0 for p, q in zip(ba.problems[:n], priors) if not ops._prior_is_empty(q)):
+            raise capi.BanetError("solve_differentiable: the prior does not fit the levels")
     dev = ba.intr.device
     B, K, pairs = ba.B, ba.K, ba.pairs
     if pairs == 1:
@@ -585,7 +651,12 @@ def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=
             w = _to_param(w, dev)
             flat += [w.reshape(w.shape[-2], w.shape[-1]), _to_param(b, dev).reshape(-1)]
         ba.mlps[li] = ops.MlpWeights([(flat[2 * i].detach(), flat[2 * i + 1].detach()) for i in range(5)], dev)
-        R, T, Wc = _LevelSolve.apply(ba, li, int(n_it), lv.src, lv.tgt, lv.depth, lv.basis, R, T, Wc, *flat)
+        pr = priors[li] if (priors is not None and li < len(priors)) else None
+        if ops._prior_is_empty(pr):
+            R, T, Wc = _LevelSolve.apply(ba, li, int(n_it), lv.src, lv.tgt, lv.depth, lv.basis, R, T, Wc, *flat)
+        else:
+            R, T, Wc = _LevelSolvePrior.apply(ba, li, int(n_it), pr, lv.src, lv.tgt, lv.depth, lv.basis, R, T, Wc, pr.Lambda, pr.eta,
+                                              pr.obs_depth, pr.obs_weight, *flat)
         if outputs is not None:
             outputs.append((R, T, Wc))
     return R, T, Wc

@@ -774,6 +774,168 @@ def prior_apply(level, prior, Wc, AtA, Atb, ws=None):
     return ws
 
 
+def _prior_is_empty(prior):
+    return prior is None or prior.scale == 0.0 or (prior.Lambda is None and prior.eta is None and prior.obs_depth is None and
+                                                   prior.obs_weight is None)
+
+
+def prior_terms(level, prior, ws=None):
+    """banet_prior_terms_f32: the once-per-level part of a Prior on its own -> (Le [B,K,K], ee [B,K]), bit-equal to what prior_apply
+    forms in its workspace: Prior(Lambda=Le, eta=ee, scale=1) applies the bits of `prior`.  The empty prior: (None, None)."""
+    L = capi.lib()
+    lv = level.c
+    B, N, K = int(lv.B), int(lv.N), int(lv.K)
+    if _prior_is_empty(prior):
+        return None, None
+    prior.check(B, N, K)
+    nb = int(L.banet_prior_workspace_bytes(ctypes.byref(lv), ctypes.byref(prior.c)))
+    if nb == 0:
+        raise capi.BanetError("prior_terms: a `bundle` level with 1 <= K <= 256 is needed (and N >= 1 with observations)")
+    dev = level.device
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, dev)
+    Le = torch.empty((B, K, K), dtype=torch.float32, device=dev)
+    ee = torch.empty((B, K), dtype=torch.float32, device=dev)
+    capi.check(L.banet_prior_terms_f32(ctypes.byref(lv), ctypes.byref(prior.c), capi.ptr(Le), capi.ptr(ee), ctypes.c_void_p(ws.data_ptr()),
+                                       ws.numel(), capi.stream()))
+    return Le, ee
+
+
+def prior_add_grad(level, Le, Wc, gAtA, gAtb, gLe=None, gee=None, gWc=None):
+    """banet_prior_add_grad_f32: the backward of one iteration's prior_apply.  gAtA [B,P,P], gAtb [B,P]: the gradients with
+    respect to the post-prior matrices (they pass through to the assembly unchanged); Le from prior_terms; Wc [B,K] that iteration's
+    coefficients.  gLe [B,K,K] / gee [B,K]: None = written (the first call of a level), else accumulated into, in place;
+    gWc [B,K]: None = zeros, and the call subtracts Le^T gAtb[m:] from it in place.  -> (gLe, gee, gWc)"""
+    lv = level.c
+    B, K = int(lv.B), int(lv.K)
+    dev = gAtA.device
+    if (gLe is None) != (gee is None):
+        raise capi.BanetError("prior_add_grad: gLe and gee are given together")
+    flags = capi.PRIOR_GRAD_OVERWRITE if gLe is None else 0
+    if gLe is None:
+        gLe = torch.empty((B, K, K), dtype=torch.float32, device=dev)
+        gee = torch.empty((B, K), dtype=torch.float32, device=dev)
+    if gWc is None:
+        gWc = torch.zeros((B, K), dtype=torch.float32, device=dev)
+    P = 6 * max(int(lv.pairs), 1) + K
+    for name, t, n in (("Le", Le, B * K * K), ("Wc", Wc, B * K), ("gAtA", gAtA, B * P * P), ("gAtb", gAtb, B * P), ("gLe", gLe, B * K * K),
+                       ("gee", gee, B * K), ("gWc", gWc, B * K)):
+        if t.numel() != n:
+            raise capi.BanetError("prior_add_grad: %s must hold %d floats" % (name, n))
+    capi.check(capi.lib().banet_prior_add_grad_f32(ctypes.byref(lv), capi.ptr(Le), capi.ptr(Wc), capi.ptr(gAtA), capi.ptr(gAtb), capi.ptr(gLe),
+                                                   capi.ptr(gee), capi.ptr(gWc), flags, capi.stream()))
+    return gLe, gee, gWc
+
+
+PRIOR_GRAD_OUTPUTS = ("gLambda", "geta", "gscale", "gobs", "gweight", "gdepth", "gbasis")
+PriorGrad = collections.namedtuple("PriorGrad", PRIOR_GRAD_OUTPUTS)
+
+
+def prior_terms_grad(level, prior, gLe, gee, Le=None, ee=None, want=PRIOR_GRAD_OUTPUTS, accumulate=False, into=None, ws=None):
+    """banet_prior_terms_grad_f32: the once-per-level backward of a Prior, from the gLe / gee that prior_add_grad accumulated ->
+    PriorGrad(gLambda [B,K,K], geta [B,K], gscale [B], gobs / gweight / gdepth [B,N], gbasis [B,N,K]); the outputs not named in
+    `want` are None, and naming one whose input the prior lacks is refused.  gscale needs Le / ee (prior_terms).  accumulate:
+    gdepth / gbasis are added into into["gdepth"] / into["gbasis"] (the dense adjoint's ddepth / dbasis; points that are not
+    counted stay untouched); otherwise they are written, zeros at those points.  A window's bits depend neither on the batch nor
+    on `want`."""
+    L = capi.lib()
+    lv = level.c
+    B, N, K = int(lv.B), int(lv.N), int(lv.K)
+    unknown = [w for w in want if w not in PRIOR_GRAD_OUTPUTS]
+    if unknown:
+        raise capi.BanetError("prior_terms_grad: unknown outputs %s" % unknown)
+    if _prior_is_empty(prior):
+        raise capi.BanetError("prior_terms_grad: the empty prior has no backward")
+    prior.check(B, N, K)
+    dev = gLe.device
+    into = into or {}
+    gin = capi.PriorGradIn()
+    gin.gLe, gin.gee = capi.ptr(gLe).value, capi.ptr(gee).value
+    gin.Le = None if Le is None else capi.ptr(Le).value
+    gin.ee = None if ee is None else capi.ptr(ee).value
+    gin.flags = capi.PRIOR_GRAD_ACCUMULATE if accumulate else 0
+    shapes = dict(gLambda=(B, K, K), geta=(B, K), gscale=(B,), gobs=(B, N), gweight=(B, N), gdepth=(B, N), gbasis=(B, N, K))
+    res, out = {}, capi.PriorGradOut()
+    for name in PRIOR_GRAD_OUTPUTS:
+        t = None
+        if name in want:
+            t = into.get(name)
+            if t is None:
+                if accumulate and name in ("gdepth", "gbasis"):
+                    raise capi.BanetError("prior_terms_grad: accumulate=True adds into into[%r]" % name)
+                t = torch.empty(shapes[name], dtype=torch.float32, device=dev)
+            elif t.numel() != int(torch.Size(shapes[name]).numel()):
+                raise capi.BanetError("prior_terms_grad: into[%r] must hold %s" % (name, shapes[name]))
+        res[name] = t
+        setattr(out, name, None if t is None else capi.ptr(t).value)
+    nb = int(L.banet_prior_terms_grad_workspace_bytes(ctypes.byref(lv), ctypes.byref(prior.c)))
+    if nb == 0:
+        raise capi.BanetError("prior_terms_grad: a `bundle` level with 1 <= K <= 256 is needed (and N >= 1 with observations)")
+    if ws is None or ws.numel() < nb:
+        ws = capi.workspace(nb, dev)
+    capi.check(L.banet_prior_terms_grad_f32(ctypes.byref(lv), ctypes.byref(prior.c), ctypes.byref(gin), ctypes.byref(out),
+                                            ctypes.c_void_p(ws.data_ptr()), ws.numel(), capi.stream()))
+    return PriorGrad(**res)
+
+
+def _prior_grad_want(prior, need):
+    """need: needs-grad flags of (Lambda, eta, obs_depth, obs_weight, depth, basis) -> the outputs to ask for"""
+    names = ("gLambda", "geta", "gobs", "gweight", "gdepth", "gbasis")
+    has = (prior.Lambda is not None, prior.eta is not None, prior.obs_depth is not None, prior.obs_weight is not None,
+           prior.obs_depth is not None, prior.obs_depth is not None)
+    return tuple(n for n, k, h in zip(names, need, has) if k and h)
+
+
+class _PriorApplyDiff(torch.autograd.Function):
+    """prior_apply, out of place, with banet_prior_add_grad_f32 + banet_prior_terms_grad_f32 as its backward; the prior's and the
+    level's tensors enter as inputs so that autograd sees them"""
+
+    @staticmethod
+    def forward(ctx, level, prior, Wc, AtA, Atb, Lambda, eta, obs, weight, depth, basis):
+        Le, ee = prior_terms(level, prior)
+        A2, b2 = AtA.clone(), Atb.clone()
+        prior_apply(level, Prior(Lambda=Le, eta=ee, scale=1.0), Wc, A2, b2)     # fl(1 x) = x: the bits of `prior`
+        ctx.level, ctx.prior = level, prior
+        ctx.shapes = [None if t is None else t.shape for t in (Wc, Lambda, eta, obs, weight, depth, basis)]
+        ctx.save_for_backward(Le, Wc)
+        ctx.set_materialize_grads(False)
+        return A2, b2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gA, gb):
+        if gA is None and gb is None:
+            return (None,) * 11
+        level, prior = ctx.level, ctx.prior
+        Le, Wc = ctx.saved_tensors
+        B, K = level.B, level.K
+        P = 6 * max(level.pairs, 1) + K
+        dev = Le.device
+        gA = torch.zeros(B, P, P, device=dev) if gA is None else capi.f32c(gA)
+        gb = torch.zeros(B, P, device=dev) if gb is None else capi.f32c(gb)
+        gLe, gee, gWc = prior_add_grad(level, Le, Wc, gA, gb)
+        want = _prior_grad_want(prior, ctx.needs_input_grad[5:])
+        g = prior_terms_grad(level, prior, gLe, gee, want=want) if want else PriorGrad(*([None] * len(PRIOR_GRAD_OUTPUTS)))
+        sW, sL, se, so, sw, sd, sb = ctx.shapes
+        rs = lambda t, s: None if (t is None or s is None) else t.reshape(s)           # noqa: E731
+        return (None, None, rs(gWc, sW) if ctx.needs_input_grad[2] else None, gA if ctx.needs_input_grad[3] else None,
+                gb if ctx.needs_input_grad[4] else None,
+                rs(g.gLambda, sL), rs(g.geta, se), rs(g.gobs, so), rs(g.gweight, sw), rs(g.gdepth, sd), rs(g.gbasis, sb))
+
+
+def prior_apply_diff(level, prior, Wc, AtA, Atb):
+    """prior_apply attached to the autograd graph, OUT of place -> (AtA', Atb'): the inputs are not modified.  Differentiable with
+    respect to AtA, Atb, Wc, the prior's Lambda / eta / obs_depth / obs_weight and the depth and basis the level was built from.
+    The backward is one banet_prior_add_grad_f32 call and one banet_prior_terms_grad_f32 call that asks only for what some input
+    needs.  Composes with dense_train.assemble_differentiable and ba_marginals_diff (marginals of the posterior with the prior as a
+    loss).  The empty prior returns (AtA, Atb) themselves."""
+    if _prior_is_empty(prior):
+        return AtA, Atb
+    depth, basis = level.keep[2], level.keep[3]
+    return _PriorApplyDiff.apply(level, prior, capi.f32c(Wc), capi.f32c(AtA), capi.f32c(Atb), prior.Lambda, prior.eta, prior.obs_depth,
+                                 prior.obs_weight, depth, basis)
+
+
 def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, params=None, prior=None):
     """banet_lm_level_ex_f32: the whole LM loop of one pyramid level, enqueued without host sync.
     params: an `lm_params(...)` value (None = the reference's defaults, legacy/ba.py:5-9).

@@ -589,6 +589,69 @@ size_t banet_lm_solve_prior_workspace_bytes(const banet_schedule_t* s, const ban
 int banet_lm_solve_prior_f32(const banet_schedule_t* s, const banet_prior_t* priors /* n_levels entries, or NULL */,
                              banet_state_t* st, banet_stream_t stream);
 
+/* (5e) the backward of (5d): training through a solve that carries a prior.  With gAtA', gAtb' the gradients with respect to the
+ *     matrices one iteration's solve was given (the post-prior ones), Wc that iteration's coefficients, m = 6 max(pairs, 1):
+ *         gAtA = gAtA', gAtb = gAtb'                               (pass through to the dense adjoint, unchanged)
+ *         gLe[i,j] += gAtA'[m+i, m+j] - gAtb'[m+i] Wc[j]           (raw, not symmetrised)
+ *         gee[i]   += gAtb'[m+i]          gWc[j] -= sum_i Le[i,j] gAtb'[m+i]
+ *     and once per level, after the iterations have accumulated gLe and gee:
+ *         gLambda = scale gLe     geta = scale gee     gscale = (sum gLe.Le + sum gee.ee) / scale
+ *         Gh = scale 1/2 (gLe + gLe^T)    gh = scale gee        (G is a mirrored sum: it takes the symmetrised gradient)
+ *         per counted point n, r = obs - depth, y = Gh b_n, p = b_n . gh, q = b_n . y:
+ *         gweight_n = q + r p     gobs_n = w p     gdepth_n -= w p     gbasis_n += w (2 y + r gh)
+ *     A point is counted as in (5d); the others get zeros, or are left untouched in accumulate mode.
+ *   banet_prior_terms_f32       the once-per-level launches of (5d) alone: Le [B,K,K] and ee [B,K] into the caller's memory, bit-equal
+ *       to what banet_prior_apply_f32 forms in its workspace (so banet_prior_apply_f32 with {Lambda = Le, eta = ee, scale = 1} adds
+ *       the bits of the original prior: fl(1 x) = x).  Workspace: banet_prior_workspace_bytes.  Errors as banet_prior_apply_f32
+ *       (NULL Le / ee: BANET_ERR_INVALID_ARG).  The empty prior writes nothing and returns BANET_OK.
+ *   banet_prior_add_grad_f32    one iteration's step, one launch, no workspace.  BANET_PRIOR_GRAD_OVERWRITE: gLe and gee are written
+ *       (the first call of a level), otherwise accumulated into; gWc always accumulates.  It reads lv->B, K, pairs and variant only.
+ *       The column sums of gWc are fixed-order fma chains joined by the wave butterfly; 16-byte accesses where K % 4 == 0 and gLe
+ *       and Wc are 16-byte aligned, 4-byte accesses of the same elements otherwise: equal bits.  NULL pointer, unknown flag bit:
+ *       BANET_ERR_INVALID_ARG; a level the term does not exist on: BANET_ERR_UNSUPPORTED.
+ *   banet_prior_terms_grad_f32  the once-per-level step.  Every output pointer is optional and a subset gives the same bits.
+ *       BANET_PRIOR_GRAD_ACCUMULATE: gdepth and gbasis are read-modify-write (the term adds into the dense adjoint's ddepth /
+ *       dbasis); without it they are written, zeros at the points that are not counted.  gLambda, geta, gscale, gobs and gweight
+ *       are always written.  An output whose input the prior does not have (gLambda / geta / gobs / gweight without Lambda / eta /
+ *       obs_depth / obs_weight; gdepth / gbasis without obs_depth), NULL gLe / gee, gscale without Le / ee, no output at all, an
+ *       unknown flag bit, an empty prior: BANET_ERR_INVALID_ARG before any launch.  gscale: one workgroup per window, float64 on
+ *       the float32 inputs, fixed order.  One preparation launch (Gh, gh into the workspace; gLambda, geta, gscale), then -- only
+ *       with observations and one of the four per-pixel outputs -- the per-pixel kernel: y = Gh b for 32-pixel tiles on
+ *       v_mfma_f32_32x32x2_f32, Gh's lower 32 x 32 blocks resident in LDS, one read of the basis row, one read-modify-write of
+ *       the gbasis row.  Workspace: Gh [B,K,K] and gh [B,K], each at a 256-byte boundary.
+ *     Enqueue only: no allocation, no synchronisation, no global state, one stream, capturable.  No float atomics; every output
+ *     element is written by exactly one lane; every summation order is a function of N, K and pairs alone: a window's bits are the
+ *     same alone and in any batch.  BANET_VERSION is unchanged by this addition: detect the entries by their symbols.          */
+#define BANET_PRIOR_GRAD_OVERWRITE 1   /* banet_prior_add_grad_f32: write gLe / gee instead of accumulating */
+#define BANET_PRIOR_GRAD_ACCUMULATE 2  /* banet_prior_terms_grad_f32: gdepth / gbasis += instead of = */
+
+typedef struct banet_prior_grad_in {
+  const float* gLe;  /* [B,K,K] accumulated by banet_prior_add_grad_f32 */
+  const float* gee;  /* [B,K] */
+  const float* Le;   /* [B,K,K] of banet_prior_terms_f32; only gscale reads it (else may be NULL) */
+  const float* ee;   /* [B,K] */
+  int32_t flags;     /* BANET_PRIOR_GRAD_ACCUMULATE or 0 */
+  int32_t reserved_; /* 0 */
+} banet_prior_grad_in_t;
+
+typedef struct banet_prior_grad_out { /* each or NULL */
+  float* gLambda; /* [B,K,K] */
+  float* geta;    /* [B,K] */
+  float* gscale;  /* [B] */
+  float* gobs;    /* [B,N] */
+  float* gweight; /* [B,N] */
+  float* gdepth;  /* [B,N] */
+  float* gbasis;  /* [B,N,K] */
+} banet_prior_grad_out_t;
+
+int banet_prior_terms_f32(const banet_level_t* lv, const banet_prior_t* pr, float* Le, float* ee, void* ws, size_t workspace_bytes,
+                          banet_stream_t stream);
+int banet_prior_add_grad_f32(const banet_level_t* lv, const float* Le, const float* Wc, const float* gAtA, const float* gAtb, float* gLe,
+                             float* gee, float* gWc, int flags, banet_stream_t stream);
+size_t banet_prior_terms_grad_workspace_bytes(const banet_level_t* lv, const banet_prior_t* pr);
+int banet_prior_terms_grad_f32(const banet_level_t* lv, const banet_prior_t* pr, const banet_prior_grad_in_t* in,
+                               const banet_prior_grad_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream);
+
 /* (6) per-level preparation -- the step immediately before the LM loop.
  *   banet_resample_f32   data [B,H,W,C], warp [B,N,2] (x,y) -> out [B,N,C]
  *       mode BANET_RESAMPLE_ZERO_PAD : tf.contrib.resampler.resampler as called at

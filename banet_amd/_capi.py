@@ -174,6 +174,12 @@ class PriorGradOut(ctypes.Structure):
     _fields_ = [("gLambda", _FP), ("geta", _FP), ("gscale", _FP), ("gobs", _FP), ("gweight", _FP), ("gdepth", _FP), ("gbasis", _FP)]
 
 
+class PosePrior(ctypes.Structure):
+    """mirror of banet_pose_prior_t (banet_pose_prior_apply_f32 and the *_pose_prior_ LM entries: all three pointers or none,
+    reserved_ = 0)"""
+    _fields_ = [("R0", _FP), ("T0", _FP), ("Lambda", _FP), ("scale", ctypes.c_float), ("reserved_", ctypes.c_int32)]
+
+
 PRIOR_GRAD_OVERWRITE, PRIOR_GRAD_ACCUMULATE = 1, 2  # banet_hip.h: BANET_PRIOR_GRAD_OVERWRITE / _ACCUMULATE
 
 ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2  # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
@@ -240,6 +246,14 @@ EXPORTS = {
     "banet_prior_terms_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.POINTER(Prior)]),
     "banet_prior_terms_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Prior), ctypes.POINTER(PriorGradIn),
                                                   ctypes.POINTER(PriorGradOut), _FP, ctypes.c_size_t, _FP]),
+    "banet_pose_prior_apply_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(PosePrior)] + [_FP] * 4 + [_FP]),
+    "banet_lm_level_pose_prior_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.POINTER(Prior), ctypes.POINTER(PosePrior)]),
+    "banet_lm_level_pose_prior_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float, ctypes.c_int,
+                                                     ctypes.POINTER(LmParams), ctypes.POINTER(Prior), ctypes.POINTER(PosePrior),
+                                                     ctypes.POINTER(State), _FP, ctypes.c_size_t, _FP]),
+    "banet_lm_solve_pose_prior_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Schedule), ctypes.POINTER(Prior), ctypes.POINTER(PosePrior)]),
+    "banet_lm_solve_pose_prior_f32": (ctypes.c_int, [ctypes.POINTER(Schedule), ctypes.POINTER(Prior), ctypes.POINTER(PosePrior),
+                                                     ctypes.POINTER(State), _FP]),
     "banet_sample_stats_grad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "banet_sample_stats_grad_det_f32": (ctypes.c_int, [_FP] * 4 + [ctypes.c_int] * 5 + [_FP] * 5 + [_FP, ctypes.c_size_t, _FP]),
     "banet_spd_solve_f32": (ctypes.c_int, [_FP] * 3 + [ctypes.c_int] * 2 + [_FP]),

@@ -113,6 +113,7 @@ int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base
   run->lv = lv;
   run->mlp = mlp;
   run->prior = PriorRun{};   // (off: lm_level_prior_plan turns it on)
+  run->pose = PosePriorRun{};   // (off: lm_level_pose_prior_plan turns it on)
   run->max_iters = max_iters;
   run->lm = early_termination && lv->variant == BANET_LEGACY_LM;
   run->role = SyrkRole{0, pl.s.Gs};
@@ -150,6 +151,33 @@ int lm_level_prior_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l
   if (!pl.on) return BANET_OK;   // the empty prior: banet_lm_level_ex_f32's launches and workspace need
   if (ws_bytes < pl.bytes) return BANET_ERR_WORKSPACE;
   run->prior = make_prior_run(lv, pr, pl, ws);
+  return BANET_OK;
+}
+
+size_t lm_level_pose_prior_bytes(const banet_level_t* lv, const banet_prior_t* pr, const banet_pose_prior_t* pp) {
+  if (pp) {   // what the entry refuses whatever the scale: a partial struct, or a prior with pointers on a level without the term
+    banet_pose_prior_t q = *pp;
+    q.scale = 1.f;
+    q.reserved_ = 0;
+    PosePriorPlan pl;
+    if (plan_pose_prior(lv, &q, &pl) != BANET_OK) return 0;
+  }
+  return lm_level_prior_bytes(lv, pr);
+}
+
+int lm_level_pose_prior_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, const banet_lm_params_t* params,
+                             const banet_prior_t* pr, const banet_pose_prior_t* pp, const banet_state_t* st, void* ws, size_t ws_bytes,
+                             LevelRun* run) {
+  int rc = plan_detail::pose_prior_struct_ok(pp);
+  if (rc != BANET_OK) return rc;
+  rc = lm_level_prior_plan(lv, mlp, l2_base, max_iters, params, pr, st, ws, ws_bytes, run);
+  if (rc != BANET_OK) return rc;
+  PosePriorPlan pl;
+  rc = plan_pose_prior(lv, pp, &pl);
+  if (rc != BANET_OK) return rc;
+  if (!pl.on) return BANET_OK;   // the empty pose prior: banet_lm_level_prior_f32's launches
+  run->pose.pl = pl;
+  run->pose.pp = *pp;
   return BANET_OK;
 }
 
@@ -191,6 +219,11 @@ int lm_level_enqueue(const LevelRun& run, hipStream_t s) {
       if (run.prior.pl.on) {   // the depth block of AtA / Atb, before the damping
         RangeScope r("prior", lv->N);
         rc = launch_prior_add(run.prior, st->Wc, w.AtA, w.Atb, s);
+        if (rc != BANET_OK) return rc;
+      }
+      if (run.pose.pl.on) {   // the pose block of AtA / Atb at the iteration's R, T, before the damping
+        RangeScope r("pose_prior", lv->N);
+        rc = launch_pose_prior_add(run.pose, st->R, st->T, w.AtA, w.Atb, s);
         if (rc != BANET_OK) return rc;
       }
       {
@@ -481,6 +514,19 @@ int banet_lm_level_prior_f32(const banet_level_t* lv, const banet_mlp_t* mlp, fl
                              size_t workspace_bytes, banet_stream_t stream) {
   LevelRun run;
   const int rc = lm_level_prior_plan(lv, mlp, l2_base, max_iters, params, pr, st, ws, workspace_bytes, &run);
+  if (rc != BANET_OK) return rc;
+  return lm_level_enqueue(run, static_cast<hipStream_t>(stream));
+}
+
+size_t banet_lm_level_pose_prior_workspace_bytes(const banet_level_t* lv, const banet_prior_t* pr, const banet_pose_prior_t* pp) {
+  return lm_level_pose_prior_bytes(lv, pr, pp);
+}
+
+int banet_lm_level_pose_prior_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters,
+                                  const banet_lm_params_t* params, const banet_prior_t* pr, const banet_pose_prior_t* pp,
+                                  banet_state_t* st, void* ws, size_t workspace_bytes, banet_stream_t stream) {
+  LevelRun run;
+  const int rc = lm_level_pose_prior_plan(lv, mlp, l2_base, max_iters, params, pr, pp, st, ws, workspace_bytes, &run);
   if (rc != BANET_OK) return rc;
   return lm_level_enqueue(run, static_cast<hipStream_t>(stream));
 }

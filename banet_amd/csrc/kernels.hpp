@@ -4,6 +4,7 @@
 #include "grid_plan.hpp"   // the grid resampler's geometry (host-only like plan.hpp)
 #include "prior_plan.hpp"  // the prior term's regions and the Gram pass's partial rows (host-only like plan.hpp)
 #include "prior_grad_plan.hpp"  // its backward: outputs, per-pixel grid, Gh / gh regions (host-only like plan.hpp)
+#include "pose_prior_plan.hpp"  // the pose prior: struct checks, the empty test, the grid (host-only like plan.hpp)
 
 namespace banet {
 
@@ -147,6 +148,14 @@ PriorRun make_prior_run(const banet_level_t* lv, const banet_prior_t* pr, const 
 int launch_prior_setup(const banet_level_t* lv, const PriorRun& run, hipStream_t s);   // once per level: Le, ee
 int launch_prior_add(const PriorRun& run, const float* Wc, float* AtA, float* Atb, hipStream_t s);   // every iteration
 
+// ---- pose_prior.hip: the SE(3) log residual on the pose block between assembly and solve (banet_pose_prior_apply_f32, the
+//      *_pose_prior_ LM entries; plan: pose_prior_plan.hpp) ----
+struct PosePriorRun {   // a planned pose prior next to its pointers; host memory only.  pl.on == 0: nothing is launched
+  PosePriorPlan pl;
+  banet_pose_prior_t pp;
+};
+int launch_pose_prior_add(const PosePriorRun& run, const float* R, const float* T, float* AtA, float* Atb, hipStream_t s);   // every iteration
+
 // ---- prep.hip --------------------------------------------------------------------------
 int launch_resample(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,
                     hipStream_t s);
@@ -279,6 +288,7 @@ struct LevelRun {   // what lm_level_plan decided; host memory only
   bool lm;     // device-side loop control (BANET_LEGACY_LM with early termination)
   SyrkRole role;   // role.on: the lambda MLP runs as a role workgroup of the SYRK launch, on role.Gs partial rows per window
   PriorRun prior;  // prior.pl.on: one launch_prior_add between assembly and solve of every iteration (lm_level_prior_plan; off otherwise)
+  PosePriorRun pose;  // pose.pl.on: one launch_pose_prior_add next to it (lm_level_pose_prior_plan; off otherwise)
 };
 // every check of banet_lm_level_ex_f32, in its order and with its return codes; launches nothing
 int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, int early_termination,
@@ -289,6 +299,12 @@ int lm_level_enqueue(const LevelRun& run, hipStream_t s);
 int lm_level_prior_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, const banet_lm_params_t* params,
                         const banet_prior_t* pr, const banet_state_t* st, void* ws, size_t ws_bytes, LevelRun* run);
 size_t lm_level_prior_bytes(const banet_level_t* lv, const banet_prior_t* pr);   // the query: 0 = unsupported / invalid
+// the same for banet_lm_level_pose_prior_f32: the pose prior's struct checks, lm_level_prior_plan, then the pose prior's plan (no
+// workspace of its own)
+int lm_level_pose_prior_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters, const banet_lm_params_t* params,
+                             const banet_prior_t* pr, const banet_pose_prior_t* pp, const banet_state_t* st, void* ws, size_t ws_bytes,
+                             LevelRun* run);
+size_t lm_level_pose_prior_bytes(const banet_level_t* lv, const banet_prior_t* pr, const banet_pose_prior_t* pp);   // 0 = unsupported / invalid
 
 // ---- schedule.hip --------------------------------------------------------------------------
 struct TraceRow {   // one level's row of banet_solve_trace_t (nullptr: not recorded) next to the state it is copied from

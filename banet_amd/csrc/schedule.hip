@@ -2,7 +2,8 @@
 // bundlenet.py:376-399 / legacy/ba.py:106-145).  Every level is validated and planned on the host first (lm_level_plan, api.hip);
 // then the levels are enqueued one after another on the caller's stream (lm_level_enqueue: the launches of banet_lm_level_ex_f32),
 // each followed by one trace launch.  No allocation, no synchronisation, one stream.  banet_lm_solve_prior_f32 is the same loop with
-// a prior per level (lm_level_prior_plan; header (5d)).
+// a prior per level (lm_level_prior_plan; header (5d)), banet_lm_solve_pose_prior_f32 with a pose prior per level as well
+// (lm_level_pose_prior_plan; header (5f)).
 #include "kernels.hpp"
 
 namespace banet {
@@ -61,16 +62,17 @@ static TraceRow trace_row(const banet_solve_trace_t* tr, const banet_level_t* lv
 }
 
 // banet_lm_solve_f32 (with_priors = false: lm_level_plan, early termination allowed) and banet_lm_solve_prior_f32 (with_priors:
-// lm_level_prior_plan with priors[l], or no prior where priors == nullptr)
-static int lm_solve_run(const banet_schedule_t* s, bool with_priors, const banet_prior_t* priors, banet_state_t* st, banet_stream_t stream) {
+// lm_level_pose_prior_plan with priors[l] and pose_priors[l], or none where the array is nullptr)
+static int lm_solve_run(const banet_schedule_t* s, bool with_priors, const banet_prior_t* priors, const banet_pose_prior_t* pose_priors,
+                        banet_state_t* st, banet_stream_t stream) {
   if (!schedule_shape_ok(s) || !s->max_iters) return BANET_ERR_INVALID_ARG;
   if (with_priors && s->early_termination != 0) return BANET_ERR_INVALID_ARG;
   // validate + plan every level; nothing is enqueued before the last one has passed
   LevelRun runs[kMaxLevels];
   for (int l = 0; l < s->n_levels; ++l) {
     const banet_mlp_t* mlp = s->mlps ? s->mlps[l] : nullptr;
-    const int rc = with_priors ? lm_level_prior_plan(&s->levels[l], mlp, s->l2_base, s->max_iters[l], s->params, priors ? &priors[l] : nullptr,
-                                                     st, s->workspace, s->workspace_bytes, &runs[l])
+    const int rc = with_priors ? lm_level_pose_prior_plan(&s->levels[l], mlp, s->l2_base, s->max_iters[l], s->params, priors ? &priors[l] : nullptr,
+                                                          pose_priors ? &pose_priors[l] : nullptr, st, s->workspace, s->workspace_bytes, &runs[l])
                                : lm_level_plan(&s->levels[l], mlp, s->l2_base, s->max_iters[l], s->early_termination, s->params, st,
                                                s->workspace, s->workspace_bytes, &runs[l]);
     if (rc != BANET_OK) return rc;
@@ -115,7 +117,7 @@ size_t banet_lm_solve_workspace_bytes(const banet_schedule_t* s) {
 }
 
 int banet_lm_solve_f32(const banet_schedule_t* s, banet_state_t* st, banet_stream_t stream) {
-  return lm_solve_run(s, false, nullptr, st, stream);
+  return lm_solve_run(s, false, nullptr, nullptr, st, stream);
 }
 
 size_t banet_lm_solve_prior_workspace_bytes(const banet_schedule_t* s, const banet_prior_t* priors) {
@@ -130,7 +132,23 @@ size_t banet_lm_solve_prior_workspace_bytes(const banet_schedule_t* s, const ban
 }
 
 int banet_lm_solve_prior_f32(const banet_schedule_t* s, const banet_prior_t* priors, banet_state_t* st, banet_stream_t stream) {
-  return lm_solve_run(s, true, priors, st, stream);
+  return lm_solve_run(s, true, priors, nullptr, st, stream);
+}
+
+size_t banet_lm_solve_pose_prior_workspace_bytes(const banet_schedule_t* s, const banet_prior_t* priors, const banet_pose_prior_t* pose_priors) {
+  if (!schedule_shape_ok(s)) return 0;
+  size_t need = 0;
+  for (int l = 0; l < s->n_levels; ++l) {
+    const size_t nb = lm_level_pose_prior_bytes(&s->levels[l], priors ? &priors[l] : nullptr, pose_priors ? &pose_priors[l] : nullptr);
+    if (nb == 0 || !same_problem(s->levels[l], s->levels[0])) return 0;
+    if (nb > need) need = nb;
+  }
+  return need;
+}
+
+int banet_lm_solve_pose_prior_f32(const banet_schedule_t* s, const banet_prior_t* priors, const banet_pose_prior_t* pose_priors,
+                                  banet_state_t* st, banet_stream_t stream) {
+  return lm_solve_run(s, true, priors, pose_priors, st, stream);
 }
 
 }  // extern "C"

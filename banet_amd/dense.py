@@ -23,10 +23,13 @@ class DensePrior:
         level_scale[l] (1/2 Wc^T Lambda Wc - eta^T Wc + 1/2 sum_n w_n (obs_n - depth_n - b_n . Wc)^2)
       coef        (Lambda [B,K,K], eta [B,K] or None), the same on every level (the coefficients are), or None
       depth_obs   one (obs, weight) pair per level, each [B,H_l,W_l] (weight None: 1), or None entries / None
-      level_scale one factor per level (default 1)."""
+      level_scale one factor per level (default 1).
+    pose = (R0 [B,pairs,3,3], T0 [B,pairs,3], Lambda [B,6 pairs,6 pairs]): additionally level_scale[l] 1/2 r^T Lambda r on the poses,
+    r = [Log(T_i o T0_i^-1)]_i (ops.PosePrior, header (5f)), the same on every level; `bundle`, and alone also `bundle_camera`."""
 
-    def __init__(self, coef=None, depth_obs=None, level_scale=None):
+    def __init__(self, coef=None, depth_obs=None, level_scale=None, pose=None):
         self.coef = coef
+        self.pose = tuple(pose) if pose is not None else None
         self.depth_obs = list(depth_obs) if depth_obs is not None else None
         self.level_scale = list(level_scale) if level_scale is not None else None
 
@@ -44,6 +47,16 @@ class DensePrior:
             w = w.reshape(p.B, p.N) if w is not None else None
             out.append(ops.Prior(Lambda, eta, o, w, scale=1.0 if self.level_scale is None else float(self.level_scale[l])))
         return out
+
+    def level_pose_priors(self, problems):
+        """-> one ops.PosePrior per level, or None without a pose prior"""
+        if self.pose is None:
+            return None
+        n = len(problems)
+        if self.level_scale is not None and len(self.level_scale) < n:
+            raise ops.capi.BanetError("DensePrior: level_scale needs one entry per level (%d)" % n)
+        R0, T0, Lambda = self.pose
+        return [ops.PosePrior(R0, T0, Lambda, scale=1.0 if self.level_scale is None else float(self.level_scale[l])) for l in range(n)]
 
 
 class DenseLevel:
@@ -153,17 +166,22 @@ class DenseBA:
         that receives, per level, the depth map depth_l + basis_l . Wc after that level, shaped like the level's depth
         (bundlenet.py:397 output_depths; `bundle` only).  prior: a DensePrior -- depth observations and / or a prior on the
         coefficients, added between assembly and solve of every iteration (`bundle` only, no early termination; the same bits on
-        the one-call path and on the per-level path); None = the call path without one."""
+        the one-call path and on the per-level path); with pose=(R0, T0, Lambda) a prior on the poses as well, or alone (then also
+        `bundle_camera`); None = the call path without one."""
         st = state if state is not None else self.new_state()
         if depth_outputs is not None and self.variant != "bundle":
             raise ops.capi.BanetError("DenseBA.solve: depth_outputs need the `bundle` variant (a depth basis)")
         n = min(len(self.problems), len(iters_per_level))
-        priors = None
+        priors = pose_priors = None
         if prior is not None:
-            if self.variant != "bundle" or early_termination:
+            pose_only = prior.pose is not None and prior.coef is None and prior.depth_obs is None
+            if early_termination or not (self.variant == "bundle" or (pose_only and self.variant == "bundle_camera")):
                 raise ops.capi.BanetError("DenseBA.solve: a prior needs the `bundle` variant and excludes early termination")
-            priors = prior.level_priors(self.problems[:n])
-            need = [ops.lm_level_workspace_bytes(p, q) for p, q in zip(self.problems[:n], priors)]
+            if not pose_only:
+                priors = prior.level_priors(self.problems[:n])
+            pose_priors = prior.level_pose_priors(self.problems[:n])
+            need = [ops.lm_level_workspace_bytes(p, priors[l] if priors is not None else None, pose_priors[l] if pose_priors is not None else None)
+                    for l, p in enumerate(self.problems[:n])]
             if min(need) == 0:
                 raise ops.capi.BanetError("DenseBA.solve: the prior does not fit the levels")
             if self.ws.numel() < max(need):
@@ -175,7 +193,7 @@ class DenseBA:
                 depth = [torch.empty((p.B, p.N), dtype=torch.float32, device=p.device) for p in self.problems[:n]]
             trace = ops.SolveTrace(n, st, fields=None if snapshots is not None else ("iters",), depth=depth)
             ops.lm_solve(self.problems[:n], self.mlps[:n], self.l2_base, list(iters_per_level[:n]), early_termination, st,
-                         ws=self.ws, params=params, trace=trace, priors=priors)
+                         ws=self.ws, params=params, trace=trace, priors=priors, pose_priors=pose_priors)
             if snapshots is not None:
                 snapshots.extend(dict(R=trace.R[l], T=trace.T[l], W=None if trace.Wc is None else trace.Wc[l],
                                       delta=trace.delta[l], lam=trace.lambda_out[l]) for l in range(n))
@@ -188,7 +206,7 @@ class DenseBA:
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record()
             li = len(counts)
-            if self.split_coarse and priors is None and self.B >= 16 and prob.N <= 1200 and li < len(self.levels):
+            if self.split_coarse and priors is None and pose_priors is None and self.B >= 16 and prob.N <= 1200 and li < len(self.levels):
                 # two half batches, the second on a side stream; joined before the next level (the state tensors are shared)
                 dev = self.intr.device
                 cur = torch.cuda.current_stream(dev)
@@ -202,7 +220,8 @@ class DenseBA:
                 cur.wait_stream(self._side)
             else:
                 ops.lm_level(prob, mlp, self.l2_base, its, early_termination, st, ws=self.ws, params=params,
-                             prior=priors[li] if (priors is not None and li < len(priors)) else None)
+                             prior=priors[li] if (priors is not None and li < len(priors)) else None,
+                             pose_prior=pose_priors[li] if (pose_priors is not None and li < len(pose_priors)) else None)
             if level_events is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
@@ -222,7 +241,8 @@ class DenseBA:
         EquationConstructionGrad).  `bundle` (K <= 256) and the pose-only `bundle_camera` variant; two-frame and multi-frame
         windows.  outputs: a list that receives (R, T, Wc) after each level, attached to the graph.  prior: a DensePrior as in
         solve(prior=) (`bundle` only, K >= 1); its tensors may require grad -- a learned obs_depth / obs_weight, the (Lambda, eta) of
-        transfer_prior -- and the levels' depth and basis receive the term's gradient as well.  None or empty: today's launches."""
+        transfer_prior -- and the levels' depth and basis receive the term's gradient as well.  None or empty: today's launches.
+        A prior with pose=: NotImplementedError (the pose prior has no backward yet)."""
         from . import dense_train
         return dense_train.solve_differentiable(self, self.levels, self.lambda_weights, iters_per_level, R, T, Wc, outputs=outputs,
                                                 prior=prior)
@@ -382,6 +402,33 @@ class DenseBA:
             scales = [q.N / float(p.N) for q in self.problems]
             return (DepthTransfer(fit.Wc, depth_map, index, hit.reshape(B, -1).sum(dim=1), fit.status),
                     DensePrior(coef=(fit.normal, fit.rhs), level_scale=scales))
+
+    def pose_prior(self, level_index, state, process_noise=None, sigma2=None, damping=0.0):
+        """What this window's solve says about its poses, as a prior for a solve that shares them: marginals(level_index, state) ->
+        DensePrior(pose=(R0, T0, Lambda), level_scale) with (R0, T0) = the state's poses (copies), Lambda = (pose_cov + Q)^-1 --
+        the 6 pairs x 6 pairs inverse in torch, float64, cast to float32 -- and level_scale[l] = N_l / N_level_index as
+        transfer_prior.  process_noise Q: None, a number (Q = q I), a tensor [6 pairs] (a diagonal), [6 pairs, 6 pairs] or
+        [B, 6 pairs, 6 pairs], in the left tangent [w; t] per target frame.  sigma2 / damping: passed to marginals; the default
+        sigma2 = None leaves pose_cov in the units of the normal equations, which is what the solve adds Lambda to.  The next
+        DenseBA (same pyramid and target frames) takes it as solve(prior=...)."""
+        p = self.problems[level_index]
+        m = 6 * p.pairs
+        with torch.no_grad():
+            cov = self.marginals(level_index, state, damping=damping, sigma2=sigma2, want=("pose_cov",)).pose_cov.double()
+            if process_noise is not None:
+                q = torch.as_tensor(process_noise, dtype=torch.float64, device=cov.device)
+                if q.dim() == 0:
+                    q = q * torch.eye(m, dtype=torch.float64, device=cov.device)
+                elif q.dim() == 1:
+                    q = torch.diag(q)
+                if q.shape[-2:] != (m, m):
+                    raise ops.capi.BanetError("DenseBA.pose_prior: process_noise must be a number, [%d], [%d,%d] or [B,%d,%d]" % (m, m, m, m, m))
+                cov = cov + q
+            Lam = torch.linalg.inv(0.5 * (cov + cov.transpose(1, 2)))
+            Lam = (0.5 * (Lam + Lam.transpose(1, 2))).float().contiguous()
+            R0 = state.R.detach().clone().reshape(p.B, p.pairs, 3, 3)
+            T0 = state.T.detach().clone().reshape(p.B, p.pairs, 3)
+        return DensePrior(pose=(R0, T0, Lam), level_scale=[q_.N / float(p.N) for q_ in self.problems])
 
     def cost_trace(self, snapshots, state0=None):
         """Did each level reduce the cost?  snapshots: what solve(snapshots=...) filled; state0: the state that solve started from

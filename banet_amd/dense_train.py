@@ -625,6 +625,9 @@ def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=
     if ba.variant not in ("bundle", "bundle_camera"):
         raise capi.BanetError("solve_differentiable: bundle / bundle_camera variants only")
     priors = None
+    if prior is not None and getattr(prior, "pose", None) is not None:
+        raise NotImplementedError("solve_differentiable: the pose prior (DensePrior(pose=...)) has no backward yet -- the gradient of "
+                                  "banet_pose_prior_apply_f32 with respect to R, T, R0, T0 and Lambda is missing")
     if prior is not None:
         if ba.variant != "bundle" or ba.K < 1:
             raise capi.BanetError("solve_differentiable: a prior needs the `bundle` variant with K >= 1")

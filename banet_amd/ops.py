@@ -936,14 +936,73 @@ def prior_apply_diff(level, prior, Wc, AtA, Atb):
                                  prior.obs_weight, depth, basis)
 
 
-def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, params=None, prior=None):
+class PosePrior:
+    """banet_pose_prior_t plus the tensors it points at: what a level's solve additionally minimises, per window,
+        scale 1/2 r^T Lambda r,   r = [Log(T_i o T0_i^-1)]_i in [phi; rho] ordering
+    R0 [B,pairs,3,3] and T0 [B,pairs,3] (any shape with these element counts) the prior poses, Lambda [B,6 pairs,6 pairs] symmetric
+    their joint information in the solve's left tangent (the inverse of ba_marginals' pose_cov).  All three or none; without
+    tensors, or with scale = 0, it is the empty pose prior (the solve without it, bit for bit)."""
+
+    def __init__(self, R0=None, T0=None, Lambda=None, scale=1.0):
+        keep = [capi.f32c(x) if x is not None else None for x in (R0, T0, Lambda)]
+        self.R0, self.T0, self.Lambda = keep
+        self.scale = float(scale)
+        self.c = capi.PosePrior()
+        for name, t in zip(("R0", "T0", "Lambda"), keep):
+            setattr(self.c, name, None if t is None else capi.ptr(t).value)   # (CPU tensors: BanetError)
+        self.c.scale = self.scale
+
+    def check(self, B, pairs):
+        m = 6 * max(int(pairs), 1)
+        for name, t, n in (("R0", self.R0, B * m // 6 * 9), ("T0", self.T0, B * m // 6 * 3), ("Lambda", self.Lambda, B * m * m)):
+            if t is not None and t.numel() != n:
+                raise capi.BanetError("PosePrior: %s holds %d values, the level (B = %d, pairs = %d) needs %d" % (name, t.numel(), B, pairs, n))
+
+
+def _pose_prior_is_empty(pp):
+    return pp is None or pp.scale == 0.0 or (pp.R0 is None and pp.T0 is None and pp.Lambda is None)
+
+
+def pose_prior_apply(level, pose_prior, R, T, AtA, Atb):
+    """banet_pose_prior_apply_f32: one iteration's step of a PosePrior between ba_assemble and ba_solve_update, IN PLACE on the pose
+    block of AtA [B,P,P] and on Atb[:, :6 pairs] at the poses R [B,pairs,3,3], T [B,pairs,3]:  AtA += scale Jr^T Lambda Jr,
+    Atb -= scale Jr^T Lambda r.  level: a LevelProblem (B, K, pairs and variant are read; `bundle` and `bundle_camera`).  No
+    workspace; the empty pose prior launches nothing."""
+    lv = level.c
+    if pose_prior is not None:
+        pose_prior.check(int(lv.B), int(lv.pairs))
+    capi.check(capi.lib().banet_pose_prior_apply_f32(ctypes.byref(lv), ctypes.byref(pose_prior.c) if pose_prior is not None else None,
+                                                     capi.ptr(R), capi.ptr(T), capi.ptr(AtA), capi.ptr(Atb), capi.stream()))
+
+
+def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, params=None, prior=None, pose_prior=None):
     """banet_lm_level_ex_f32: the whole LM loop of one pyramid level, enqueued without host sync.
     params: an `lm_params(...)` value (None = the reference's defaults, legacy/ba.py:5-9).
     prior: a `Prior` (banet_lm_level_prior_f32: its term is added between assembly and solve of every iteration; `bundle` levels,
-    no early termination); None = the call path without one."""
+    no early termination); None = the call path without one.
+    pose_prior: a `PosePrior` (banet_lm_level_pose_prior_f32, with `prior` or without; `bundle` and `bundle_camera` levels, no early
+    termination); None = the call path without one."""
     L = capi.lib()
     if mlp is not None:
         mlp.check(level.C)
+    if pose_prior is not None:
+        if early_termination:
+            raise capi.BanetError("lm_level: a pose prior excludes early termination")
+        pose_prior.check(level.B, level.pairs)
+        if prior is not None:
+            prior.check(level.B, level.N, level.K)
+        pc = ctypes.byref(prior.c) if prior is not None else None
+        nb = L.banet_lm_level_pose_prior_workspace_bytes(ctypes.byref(level.c), pc, ctypes.byref(pose_prior.c))
+        if nb == 0:
+            raise capi.BanetError("lm_level: unsupported level shape, a prior on a level without a depth basis, or a pose prior on a "
+                                  "legacy variant / with only some of R0, T0, Lambda")
+        if ws is None or ws.numel() < nb:
+            ws = capi.workspace(nb, level.device)
+        capi.check(L.banet_lm_level_pose_prior_f32(ctypes.byref(level.c), ctypes.byref(mlp.c) if mlp is not None else None, float(l2_base),
+                                                   int(max_iters), ctypes.byref(params) if params is not None else None, pc,
+                                                   ctypes.byref(pose_prior.c), ctypes.byref(state.c), ctypes.c_void_p(ws.data_ptr()),
+                                                   ws.numel(), capi.stream()))
+        return ws
     if prior is not None:
         if early_termination:
             raise capi.BanetError("lm_level: a prior excludes early termination")
@@ -969,7 +1028,10 @@ def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, 
     return ws
 
 
-def lm_level_workspace_bytes(level, prior=None):
+def lm_level_workspace_bytes(level, prior=None, pose_prior=None):
+    if pose_prior is not None:
+        return capi.lib().banet_lm_level_pose_prior_workspace_bytes(ctypes.byref(level.c), ctypes.byref(prior.c) if prior is not None else None,
+                                                                    ctypes.byref(pose_prior.c))
     if prior is not None:
         return capi.lib().banet_lm_level_prior_workspace_bytes(ctypes.byref(level.c), ctypes.byref(prior.c))
     return capi.lib().banet_lm_level_workspace_bytes(ctypes.byref(level.c))
@@ -1036,13 +1098,40 @@ def lm_solve_workspace_bytes(levels):
     return capi.lib().banet_lm_solve_workspace_bytes(ctypes.byref(s))
 
 
-def lm_solve(levels, mlps, l2_base, iters, early_termination, state, ws=None, params=None, trace=None, priors=None):
+def lm_solve(levels, mlps, l2_base, iters, early_termination, state, ws=None, params=None, trace=None, priors=None, pose_priors=None):
     """banet_lm_solve_f32: every level of a coarse -> fine schedule in ONE call -- the sequence of lm_level calls, bit for bit,
     with the state after each level recorded in `trace` (a SolveTrace, or None).  levels / mlps / iters: one LevelProblem,
     MlpWeights (or None) and iteration count per level.  All levels are validated before anything is enqueued.
-    priors: one `Prior` or None per level (banet_lm_solve_prior_f32; no early termination); None = the call path without."""
+    priors: one `Prior` or None per level (banet_lm_solve_prior_f32; no early termination); None = the call path without.
+    pose_priors: one `PosePrior` or None per level (banet_lm_solve_pose_prior_f32, with `priors` or without; no early termination);
+    None = the call path without."""
     L = capi.lib()
     s, keep = _schedule(levels, mlps, l2_base, iters, early_termination, params, trace)
+    if pose_priors is not None:
+        n = len(levels)
+        if len(pose_priors) != n or (priors is not None and len(priors) != n):
+            raise capi.BanetError("lm_solve: %d pose priors and %s priors for %d levels" % (len(pose_priors), "no" if priors is None else len(priors), n))
+        if early_termination:
+            raise capi.BanetError("lm_solve: pose priors exclude early termination")
+        pp = (capi.PosePrior * n)()                        # (a zeroed entry is the empty pose prior)
+        pr = (capi.Prior * n)() if priors is not None else None
+        for i in range(n):
+            if pose_priors[i] is not None:
+                pose_priors[i].check(levels[i].B, levels[i].pairs)
+                pp[i] = pose_priors[i].c
+            if priors is not None and priors[i] is not None:
+                priors[i].check(levels[i].B, levels[i].N, levels[i].K)
+                pr[i] = priors[i].c
+        nb = L.banet_lm_solve_pose_prior_workspace_bytes(ctypes.byref(s), pr, pp)
+        if nb == 0:
+            raise capi.BanetError("lm_solve: unsupported level shape, levels that disagree in B / K / pairs / variant / policy, a prior on "
+                                  "a level without a depth basis, or a pose prior on a legacy variant / with only some of R0, T0, Lambda")
+        if ws is None or ws.numel() < nb:
+            ws = capi.workspace(nb, levels[0].device)
+        s.workspace, s.workspace_bytes = ws.data_ptr(), ws.numel()
+        capi.check(L.banet_lm_solve_pose_prior_f32(ctypes.byref(s), pr, pp, ctypes.byref(state.c), capi.stream()))
+        del keep
+        return ws
     if priors is not None:
         n = len(levels)
         if len(priors) != n:

@@ -652,6 +652,64 @@ size_t banet_prior_terms_grad_workspace_bytes(const banet_level_t* lv, const ban
 int banet_prior_terms_grad_f32(const banet_level_t* lv, const banet_prior_t* pr, const banet_prior_grad_in_t* in,
                                const banet_prior_grad_out_t* out, void* ws, size_t workspace_bytes, banet_stream_t stream);
 
+/* (5f) a pose prior inside the LM loop: a motion-model, odometry or IMU pose, or the previous window's posterior on the frames it
+ *     shares with this one (banet_ba_marginals_f32's pose_cov, inverted).  BANET_BUNDLE levels (K >= 1) and the pose-only
+ *     BANET_BUNDLE_CAMERA (K == 0), dense or sparse, up to 8 target frames.  The update convention is the solve's: delta = [w; t],
+ *     R' = exp(w) R, T' = V(w) t + exp(w) T, i.e. T' = Exp(delta) o T with Exp([phi; rho]) = (exp(phi), V(phi) rho) -- a left
+ *     perturbation, the tangent pose_cov is expressed in.  Per window, with prior poses (R0_i, T0_i), i < pairs, and a joint
+ *     information matrix Lambda [m,m], m = 6 max(pairs, 1) (symmetric; positive semi-definite expected, not checked), the solve
+ *     additionally minimises scale 1/2 r^T Lambda r:
+ *         E_i = T_i o T0_i^-1:  Re = R_i R0_i^T,  te = T_i - Re T0_i        r_i = Log(E_i) = [phi; rho],  rho = V(phi)^-1 te
+ *         Jr  = blockdiag_i J_l(r_i)^-1,   J_l^-1 = [[J^-1, 0], [-J^-1 Q J^-1, J^-1]],   J = V(phi),   Q = Q(rho, phi) of the
+ *               SE(3) left Jacobian in closed form (Barfoot, State Estimation for Robotics), rotation first
+ *         AtA[0:m, 0:m] += scale Jr^T Lambda Jr         Atb[0:m] -= scale Jr^T Lambda r           (Gauss-Newton; row stride P)
+ *     between (3) and (4) of every iteration at that iteration's R, T: before the damping, which therefore sees the prior on the
+ *     diagonal.  lambda is still predicted from the feature residuals alone.  The angle is atan2(|vee(Re - Re^T)| / 2,
+ *     (tr Re - 1) / 2); series below |phi| = 1e-3 (theta / sin theta) and 0.5 (the coefficients of J^-1 and Q).  Supported range:
+ *     |phi| <= 3.0; beyond it the outputs are finite and nothing more.  At Re = I and te = 0 exactly (R = R0 = I, T = T0):
+ *     Jr = I and r = 0 exactly, the block gets fl(scale Lambda) and Atb keeps its bits.
+ *     One launch per iteration, ba_pose_prior_add_kernel: one workgroup of four waves per window whatever the shape, r_i and
+ *     Jr_i in LDS, no workspace, no once-per-level pass, no atomics, every output element written by exactly one lane, 4-byte
+ *     accesses to AtA.  Every summation order depends on pairs only: a window's bits are the same alone and in any batch.
+ *     The EMPTY pose prior: pp == NULL, all three pointers NULL, or scale == 0.  banet_pose_prior_apply_f32 then launches
+ *     nothing; banet_lm_level_pose_prior_f32 is then exactly banet_lm_level_prior_f32 and banet_lm_solve_pose_prior_f32 exactly
+ *     banet_lm_solve_prior_f32 (same launches, same bits, same workspace need).
+ *     BANET_ERR_INVALID_ARG, decided before any launch: some but not all of R0 / T0 / Lambda; a scale that is negative or not
+ *     finite; reserved_ != 0 (whatever the scale); NULL R / T / AtA / Atb (banet_pose_prior_apply_f32); everything
+ *     banet_lm_level_prior_f32 / banet_lm_solve_prior_f32 refuse, with their codes (pr keeps the rules of (5d): a coefficient
+ *     prior on a camera level is still BANET_ERR_UNSUPPORTED); s->early_termination != 0.  A pose prior that is not empty on a
+ *     legacy variant or a window of more than 8 target frames: BANET_ERR_UNSUPPORTED, and a query of 0.
+ *     Workspace: none of its own -- banet_lm_level_pose_prior_workspace_bytes(lv, pr, pp) == banet_lm_level_prior_workspace_bytes(lv,
+ *     pr) wherever the entry accepts pp's pointers (the scale is not read), and the solve query is the maximum over the levels.
+ *     banet_pose_prior_apply_f32 is one iteration's step on the caller's AtA [B,P,P] / Atb [B,P] at R [B,pairs,3,3], T [B,pairs,3],
+ *     in place; it reads lv->B, K, pairs and variant and nothing else of the level.
+ *     banet_lm_solve_pose_prior_f32: priors[l] and pose_priors[l] belong to levels[l] (either array may be NULL: no level has
+ *     one); all or nothing -- a bad prior on the last level enqueues nothing; bit-identical to the sequence of
+ *     banet_lm_level_pose_prior_f32 calls plus the trace copies.
+ *     Enqueue only: no allocation, no synchronisation, no global state, one stream, capturable.  BANET_VERSION is unchanged by this
+ *     addition: detect the entries by their symbols.                                                                           */
+typedef struct banet_pose_prior {
+  const float* R0;      /* [B,pairs,3,3] */
+  const float* T0;      /* [B,pairs,3] */
+  const float* Lambda;  /* [B,m,m] symmetric, m = 6 max(pairs, 1) */
+  float scale;          /* finite, >= 0 */
+  int32_t reserved_;    /* 0 */
+} banet_pose_prior_t;
+
+int banet_pose_prior_apply_f32(const banet_level_t* lv, const banet_pose_prior_t* pp, const float* R, const float* T, float* AtA,
+                               float* Atb, banet_stream_t stream);
+
+size_t banet_lm_level_pose_prior_workspace_bytes(const banet_level_t* lv, const banet_prior_t* pr, const banet_pose_prior_t* pp);
+int banet_lm_level_pose_prior_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, int max_iters,
+                                  const banet_lm_params_t* params, const banet_prior_t* pr, const banet_pose_prior_t* pp,
+                                  banet_state_t* st, void* ws, size_t workspace_bytes, banet_stream_t stream);
+
+size_t banet_lm_solve_pose_prior_workspace_bytes(const banet_schedule_t* s, const banet_prior_t* priors,
+                                                 const banet_pose_prior_t* pose_priors);
+int banet_lm_solve_pose_prior_f32(const banet_schedule_t* s, const banet_prior_t* priors /* n_levels entries, or NULL */,
+                                  const banet_pose_prior_t* pose_priors /* n_levels entries, or NULL */, banet_state_t* st,
+                                  banet_stream_t stream);
+
 /* (6) per-level preparation -- the step immediately before the LM loop.
  *   banet_resample_f32   data [B,H,W,C], warp [B,N,2] (x,y) -> out [B,N,C]
  *       mode BANET_RESAMPLE_ZERO_PAD : tf.contrib.resampler.resampler as called at

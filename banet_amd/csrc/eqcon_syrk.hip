@@ -88,7 +88,10 @@ __global__ __launch_bounds__(kBlock) void eq_pixel_records_kernel(const float* _
       const float l11 = sqrtf(fmaxf(q.m11, 0.f));
       const float i11 = l11 > 0.f ? 1.f / l11 : 0.f;
       const float l21 = q.m12 * i11;
-      const float l22 = sqrtf(fmaxf(q.m22 - l21 * l21, 0.f));
+      // m22 - l21^2 cancels on a nearly rank-1 M and may round to <= 0 while g2 - l21 h0 does not: a zero l22 would then drop
+      // (g2 - l21 h0) j_y from Atb, up to sqrt(eps) of the pixel's share.  The floor 2^-24 m22 is below the rounding error of the
+      // difference (AtA moves by less than it already had), keeps h1 l22 = g2 - l21 h0, and is 0 where m22 is (gy = 0, G = 0).
+      const float l22 = sqrtf(fmaxf(q.m22 - l21 * l21, 0x1p-24f * q.m22));
       const float i22 = l22 > 0.f ? 1.f / l22 : 0.f;
       const float h0 = q.g1 * i11;
       const float h1 = (q.g2 - l21 * h0) * i22;

@@ -21,8 +21,13 @@ static int check_level(const banet_level_t* lv) {
   return BANET_OK;
 }
 
-// (LevelWs: kernels.hpp)
-static LevelWs carve_level(const banet_level_t* lv, const AsmPlan& pl, void* ws) {
+// the solve's plan for a level: P = 6 pairs + K unknowns, the level's variant and flags, lm.solver
+static int plan_level_solve(const banet_level_t* lv, int solver, SolvePlan* sp) {
+  return plan_solve(lv->variant, 6 * npairs(lv) + lv->K, lv->C, solver, lv->flags, sp);
+}
+
+// (LevelWs: kernels.hpp)  sp: plan_level_solve's (the matrix of a big solve is the last region)
+static LevelWs carve_level(const banet_level_t* lv, const AsmPlan& pl, const SolvePlan& sp, void* ws) {
   LevelWs w;
   char* p = static_cast<char*>(ws);
   Arena ar;
@@ -37,8 +42,7 @@ static LevelWs carve_level(const banet_level_t* lv, const AsmPlan& pl, void* ws)
   w.nvalid = reinterpret_cast<float*>(take((size_t)lv->B * sizeof(float)));
   w.ctl = reinterpret_cast<LmCtl*>(take((size_t)lv->B * sizeof(LmCtl)));
   w.mlp_y = reinterpret_cast<float*>(take((size_t)lv->B * sizeof(float)));
-  const size_t big = solve_big_bytes(lv->B, pl.P, lv->C);
-  w.bigA = big ? reinterpret_cast<float*>(take(big)) : nullptr;
+  w.bigA = sp.big ? reinterpret_cast<float*>(take((size_t)lv->B * sp.big_floats * sizeof(float))) : nullptr;
   w.total = ar.off;
   return w;
 }
@@ -69,8 +73,8 @@ static SolveArgs make_solve_args(const banet_level_t* lv, const banet_mlp_t* mlp
   a.nqueue = 0;
   a.bigA = nullptr;
   a.mlp_y = nullptr;
-  a.flags = lv->flags;
   banet_lm_params_default(&a.lm);
+  a.pl = SolvePlan{};   // (the caller's: plan_level_solve)
   return a;
 }
 
@@ -96,20 +100,26 @@ int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base
   AsmPlan& pl = run->pl;
   rc = plan_assemble(lv, num_cus(), &pl);
   if (rc != BANET_OK) return rc;
+  // the solve, planned once per level (an lm.solver that is refused below plans like BANET_SOLVER_QR; the workspace need does
+  // not depend on it)
+  SolvePlan sp;
+  const int solve_rc = plan_level_solve(lv, params ? params->solver : BANET_SOLVER_QR, &sp);
   if (!ws || !aligned256(ws)) return BANET_ERR_WORKSPACE;
   LevelWs& w = run->w;
-  w = carve_level(lv, pl, ws);
+  w = carve_level(lv, pl, sp, ws);
   if (ws_bytes < w.total) return BANET_ERR_WORKSPACE;
   SolveArgs& a = run->a;
   a = make_solve_args(lv, mlp, l2_base, w.AtA, w.Atb, w.absres, w.nvalid, st);
   a.max_iters = max_iters;
   a.bigA = w.bigA;
+  a.pl = sp;
   if (params) {
     if (params->solver != BANET_SOLVER_QR && params->solver != BANET_SOLVER_INVERSE) return BANET_ERR_INVALID_ARG;
     if (!(params->angle_change >= 0.f) || !(params->translation_change >= 0.f) || !(params->residual_ratio > 0.f))
       return BANET_ERR_INVALID_ARG;   // also rejects NaN
     a.lm = *params;
   }
+  if (solve_rc != BANET_OK) return solve_rc;   // vectors and scratch alone beyond the LDS (hundreds of target frames)
   run->lv = lv;
   run->mlp = mlp;
   run->prior = PriorRun{};   // (off: lm_level_prior_plan turns it on)
@@ -134,8 +144,10 @@ int lm_level_plan(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base
 size_t lm_level_prior_bytes(const banet_level_t* lv, const banet_prior_t* pr) {
   AsmPlan apl;
   if (plan_assemble(lv, num_cus(), &apl) != BANET_OK) return 0;
+  SolvePlan sp;
+  (void)plan_level_solve(lv, BANET_SOLVER_QR, &sp);
   PriorPlan pl;
-  if (plan_prior_layout(lv, pr, carve_level(lv, apl, nullptr).total, &pl) != BANET_OK) return 0;
+  if (plan_prior_layout(lv, pr, carve_level(lv, apl, sp, nullptr).total, &pl) != BANET_OK) return 0;
   return pl.bytes;
 }
 
@@ -234,6 +246,31 @@ int lm_level_enqueue(const LevelRun& run, hipStream_t s) {
     }
   }
   return BANET_OK;
+}
+
+static size_t solve_update_ws_bytes(int B, const SolvePlan& sp) { return align_up((size_t)B * sp.big_floats * sizeof(float), 256); }
+
+// banet_ba_solve_update_f32 (has_ws = false) and banet_ba_solve_update_ws_f32: the checks, the plan, the launch.  A system whose
+// matrix does not fit the LDS is BANET_ERR_UNSUPPORTED without a workspace, and BANET_ERR_WORKSPACE with one that is missing, too
+// small or misaligned.
+static int solve_update(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, const float* AtA, const float* Atb,
+                        const float* absres, const float* nvalid, banet_state_t* st, bool has_ws, void* ws, size_t ws_bytes,
+                        banet_stream_t stream) {
+  if (!lv || !AtA || !Atb || !absres || !nvalid) return BANET_ERR_INVALID_ARG;
+  if (lv->variant < BANET_LEGACY_LM || lv->variant > BANET_BUNDLE || lv->B <= 0 || lv->N <= 0 || lv->C <= 0 || lv->K < 0 ||
+      lv->pairs < 0)
+    return BANET_ERR_INVALID_ARG;
+  int rc = check_state(lv, mlp, st);
+  if (rc != BANET_OK) return rc;
+  SolveArgs a = make_solve_args(lv, mlp, l2_base, AtA, Atb, absres, nvalid, st);
+  rc = plan_level_solve(lv, a.lm.solver, &a.pl);
+  if (a.pl.big) {
+    if (!has_ws) return BANET_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < solve_update_ws_bytes(lv->B, a.pl) || !aligned256(ws)) return BANET_ERR_WORKSPACE;
+    a.bigA = static_cast<float*>(ws);
+  }
+  if (rc != BANET_OK) return rc;
+  return launch_solve(a, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace banet
@@ -446,43 +483,28 @@ int banet_basis_fit_f32(const banet_level_t* lv, const float* target, const floa
 int banet_ba_solve_update_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, const float* AtA,
                               const float* Atb, const float* absres, const float* nvalid, banet_state_t* st,
                               banet_stream_t stream) {
-  if (!lv || !AtA || !Atb || !absres || !nvalid) return BANET_ERR_INVALID_ARG;
-  if (lv->variant < BANET_LEGACY_LM || lv->variant > BANET_BUNDLE || lv->B <= 0 || lv->N <= 0 || lv->C <= 0 || lv->K < 0 ||
-      lv->pairs < 0)
-    return BANET_ERR_INVALID_ARG;
-  const int rc = check_state(lv, mlp, st);
-  if (rc != BANET_OK) return rc;
-  SolveArgs a = make_solve_args(lv, mlp, l2_base, AtA, Atb, absres, nvalid, st);
-  return launch_solve(a, static_cast<hipStream_t>(stream));
+  return solve_update(lv, mlp, l2_base, AtA, Atb, absres, nvalid, st, false, nullptr, 0, stream);
 }
 
 size_t banet_ba_solve_update_workspace_bytes(const banet_level_t* lv) {
   if (!lv || lv->B <= 0 || lv->C <= 0 || lv->K < 0 || lv->pairs < 0) return 0;
-  return align_up(solve_big_bytes(lv->B, 6 * npairs(lv) + lv->K, lv->C), 256);
+  SolvePlan sp;
+  (void)plan_level_solve(lv, BANET_SOLVER_QR, &sp);   // (big / big_floats: filled whatever it returns)
+  return solve_update_ws_bytes(lv->B, sp);
 }
 
 int banet_ba_solve_update_ws_f32(const banet_level_t* lv, const banet_mlp_t* mlp, float l2_base, const float* AtA,
                                  const float* Atb, const float* absres, const float* nvalid, banet_state_t* st, void* ws,
                                  size_t ws_bytes, banet_stream_t stream) {
-  if (!lv || !AtA || !Atb || !absres || !nvalid) return BANET_ERR_INVALID_ARG;
-  if (lv->variant < BANET_LEGACY_LM || lv->variant > BANET_BUNDLE || lv->B <= 0 || lv->N <= 0 || lv->C <= 0 || lv->K < 0 ||
-      lv->pairs < 0)
-    return BANET_ERR_INVALID_ARG;
-  const int rc = check_state(lv, mlp, st);
-  if (rc != BANET_OK) return rc;
-  SolveArgs a = make_solve_args(lv, mlp, l2_base, AtA, Atb, absres, nvalid, st);
-  const size_t need = banet_ba_solve_update_workspace_bytes(lv);
-  if (need > 0) {
-    if (!ws || ws_bytes < need || !aligned256(ws)) return BANET_ERR_WORKSPACE;
-    a.bigA = static_cast<float*>(ws);
-  }
-  return launch_solve(a, static_cast<hipStream_t>(stream));
+  return solve_update(lv, mlp, l2_base, AtA, Atb, absres, nvalid, st, true, ws, ws_bytes, stream);
 }
 
 size_t banet_lm_level_workspace_bytes(const banet_level_t* lv) {
   AsmPlan pl;
   if (plan_assemble(lv, num_cus(), &pl) != BANET_OK) return 0;
-  return carve_level(lv, pl, nullptr).total;
+  SolvePlan sp;
+  (void)plan_level_solve(lv, BANET_SOLVER_QR, &sp);   // (big / big_floats: filled whatever it returns)
+  return carve_level(lv, pl, sp, nullptr).total;
 }
 
 void banet_lm_params_default(banet_lm_params_t* p) {

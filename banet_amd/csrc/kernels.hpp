@@ -5,6 +5,7 @@
 #include "prior_plan.hpp"  // the prior term's regions and the Gram pass's partial rows (host-only like plan.hpp)
 #include "prior_grad_plan.hpp"  // its backward: outputs, per-pixel grid, Gh / gh regions (host-only like plan.hpp)
 #include "pose_prior_plan.hpp"  // the pose prior: struct checks, the empty test, the grid (host-only like plan.hpp)
+#include "solve_plan.hpp"  // the solve: method, LDS-or-workspace switch, LDS layout (host-only like plan.hpp)
 
 namespace banet {
 
@@ -199,7 +200,8 @@ int launch_eq_grad_fast(const float* J, const float* G, const float* d, const fl
 int launch_eq_grad(const float* J, const float* G, const float* d, const float* g0, const float* g1, float* gJ,
                    float* gG, float* gd, int B, int N, int C, int P, hipStream_t s);
 
-// ---- solve.hip -------------------------------------------------------------------------
+// ---- solve.hip (ba_solve_update_kernel, the control kernels) and spd_solve.hip (spd_solve_kernel); plan: solve_plan.hpp, shared
+//      device code: solve_common.hpp ----
 struct LmCtl {  // per-window loop state of the legacy early-termination LM (device memory)
   int32_t active;
   int32_t pending;
@@ -223,17 +225,15 @@ struct SolveArgs {
   const float* nvalid;
   banet_state_t st;
   LmCtl* ctl;  // nullptr: fixed-count mode (every call performs one update)
-  float* bigA; // workspace for the normal matrix when it does not fit in LDS (solve_big_bytes), else nullptr
+  float* bigA; // pl.big: workspace for the normal matrix, B * pl.big_floats floats; else nullptr
   int* queue;  // LM loop: the next gather's tile-queue heads, zeroed by this kernel (saves a memset per iteration)
   int nqueue;  // words per window
   const float* mlp_y;   // [B] lambda-MLP outputs precomputed by the SYRK launch's role workgroups, or nullptr
   banet_lm_params_t lm;   // run-time LM configuration (legacy/ba.py:5-9)
-  int flags;              // banet_level_t.flags (development switches: kDevSolveLdltOnly)
+  SolvePlan pl;           // plan_solve(variant, P, C, lm.solver, the level's flags): method, strides, LDS offsets
 };
-int launch_solve(const SolveArgs& a, hipStream_t s);
-int launch_spd_solve(const float* A, const float* rhs, float* x, int B, int P, hipStream_t s);   // 32 <= P, matrix in LDS
-bool spd_solve_fits(int P);     // launch_spd_solve accepts this size
-size_t solve_big_bytes(int B, int P, int C);
+int launch_solve(const SolveArgs& a, hipStream_t s);   // only launches: a.pl accepted by plan_solve, a.bigA given where a.pl.big
+int launch_spd_solve(const float* A, const float* rhs, float* x, int B, int P, hipStream_t s);   // plan_spd_solve's codes, then the launch
 void launch_ctl_init(LmCtl* ctl, int32_t* iters, int B, hipStream_t s);
 void launch_zero_iters(int32_t* iters, int B, hipStream_t s);
 

@@ -8,7 +8,7 @@
 // upstream gradients of the updated state (gR', gT', gW'):
 //   small_pre_kernel    one workgroup per window: lambda MLP forward (activations kept), lambda; the adjoint of the SE(3) / W update
 //                       -> dL/d(R, T) (direct part) and dL/dsol; the damped matrix A and the right-hand side dL/dsol for the solve
-//   spd_solve_kernel    (solve.hip) lam_adj = A^-1 dL/dsol          [P < 32 -- bundle with 6 pairs + K < 32, i.e. K <= 25 on two-frame
+//   spd_solve_kernel    (spd_solve.hip) lam_adj = A^-1 dL/dsol          [P < 32 -- bundle with 6 pairs + K < 32, i.e. K <= 25 on two-frame
 //                       windows, and camera windows of up to 5 target frames (P = 6 .. 30): a Cholesky in double on one thread of
 //                       small_post_kernel instead]
 //   small_post_kernel   one workgroup per window: dL/dAtb = lam_adj, dL/dA = -lam_adj sol^T (implicit function theorem, A = A^T),
@@ -375,8 +375,9 @@ bool small_step_supported(int variant, int B, int N, int C, int K, int pairs) {
   } else {
     return false;
   }
-  if (P >= 32) return spd_solve_fits(P);      // the solve runs on spd_solve_kernel: its matrix must fit the LDS
-  return true;
+  if (P < kGrid) return true;                 // the Cholesky of small_post_kernel
+  SolvePlan sp;                               // the solve runs on spd_solve_kernel: its matrix must fit the LDS
+  return plan_spd_solve(P, &sp) == BANET_OK;
 }
 
 size_t small_step_workspace_bytes(int variant, int B, int N, int C, int K, int pairs) {

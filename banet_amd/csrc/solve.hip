@@ -1,6 +1,6 @@
 // lambda prediction, damping, linear solve and SE(3)/W update -- one workgroup per window.
 //
-// Restates (citations under /root/reference):
+// Restates (citations: files of the reference implementation):
 //   avg residual & lambda MLP    bundlenet.py:165-173,241-253 ; legacy/ba.py:187-190,266-275
 //   damping                      bundlenet.py:181-182,264-266 ; legacy/ba.py:200-201,285-286
 //   solve                        tf.matrix_solve (LU, partial pivoting) bundlenet.py:183,267 ;
@@ -9,66 +9,17 @@
 //   accept / terminate           legacy/ba.py:132-140,304-345
 // The matrix lives in LDS (P <= 134 -> 72 KB of the 160 KB per CU); larger systems (K = 256, many frames) keep it in
 // the caller's workspace (template<bool BIG>, workgroup-private and L2-resident).
-#include <type_traits>
-
-#include "kernels.hpp"
+// Which solver runs, the LDS-or-workspace switch and every offset of the dynamic LDS are decided on the host: plan_solve
+// (solve_plan.hpp); the plan arrives in SolveArgs::pl.  Here: ba_solve_update_kernel with the one-thread 6 x 6 solvers, the
+// register LU and the conjugate gradients, the two control kernels and launch_solve.  The blocked LDL^T and the wave reductions:
+// solve_common.hpp (shared with spd_solve.hip).
 #include "mlp.hpp"
+#include "solve_common.hpp"
 
 namespace banet {
 
-#ifdef BANET_TIMING
-__device__ __forceinline__ unsigned long long stick() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define STICK(v) const unsigned long long v = stick()
-#else
-#define STICK(v)
-#endif
-
-constexpr int kSolveThreads = 1024;   // 16 waves: 4 per SIMD, so the latency-bound phases overlap
-[[maybe_unused]] constexpr int kSolveWaves = kSolveThreads / 64;
-constexpr int kGrid = 32;              // 2-D cyclic thread grid of the register-resident solvers
-
 // selu / block_sum_t / mlp_layer_t: mlp.hpp (shared with the MLP role workgroup of the SYRK launch)
 __device__ __forceinline__ float block_sum(float v, float* sred) { return block_sum_t<kSolveThreads>(v, sred); }
-
-// sum over the 64 lanes without the LDS crossbar; every lane gets the total
-__device__ __forceinline__ float wave_sum_fast(float v) {
-  v = row16_sum(v);
-  v = bfly_merge(v, v, 16);
-  return bfly_merge(v, v, 32);
-}
-
-// max / min over the 64 lanes on DPP + permlane swaps (every lane gets the result)
-__device__ __forceinline__ float wave_max_fast(float v) {
-  v = fmaxf(v, dpp_mov<kDppRor8>(v));
-  v = fmaxf(v, dpp_mov<kDppHalfMirror>(v));
-  v = fmaxf(v, dpp_mov<kDppXor2>(v));
-  v = fmaxf(v, dpp_mov<kDppXor1>(v));
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  v = fmaxf(a, b);
-  a = v;
-  b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return fmaxf(a, b);
-}
-__device__ __forceinline__ int wave_min_fast(int v) {
-  auto dpp = [](int x, auto ctrl) { return __builtin_amdgcn_update_dpp(0x7fffffff, x, decltype(ctrl)::value, 0xF, 0xF, false); };
-  v = min(v, dpp(v, std::integral_constant<int, kDppRor8>{}));
-  v = min(v, dpp(v, std::integral_constant<int, kDppHalfMirror>{}));
-  v = min(v, dpp(v, std::integral_constant<int, kDppXor2>{}));
-  v = min(v, dpp(v, std::integral_constant<int, kDppXor1>{}));
-  int a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  v = min(a, b);
-  a = v;
-  b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return min(a, b);
-}
 
 __device__ __forceinline__ void mlp_layer(const float* in, float* out, const float* __restrict__ Wt, const float* __restrict__ bias,
                                           int nin, int nout, int act, float* sPart, float* sred) {
@@ -79,7 +30,7 @@ __device__ __forceinline__ void mlp_layer(const float* in, float* out, const flo
 // tf.linalg.solve on the triangular factor.  Round 6: the matrix lives in REGISTERS (every loop has compile-time bounds and is
 // unrolled) -- the LDS-resident loop form cost ~400 dependent LDS round trips and, with inverse_solve_small's dynamically indexed
 // rows, 644 scratch instructions in the kernel (round-5 review): same operations in the same order, so the same bits.
-__device__ void qr_solve_small(const float* A_lds, int ld, const float* rhs_in, int /*n = 6*/, float* x) {
+__device__ void qr_solve_small(const float* A_lds, int ld, const float* rhs_in, float* x) {
   constexpr int n = 6;
   float A[n][n], rhs[n];
 #pragma unroll
@@ -288,230 +239,6 @@ __device__ void lu_solve_regs(float* A, int ld, int n, float* x, int* order, flo
   __syncthreads();
 }
 
-// --------------------------------------------------------------------------------------
-// Blocked LDL^T for the bundle variants (32 <= n): the damped normal matrix is symmetric positive
-// definite (PSD Gram matrix + positive damping), so the pivoted LU of tf.matrix_solve
-// (bundlenet.py:267) reduces to elimination in natural order; same solution up to rounding
-// (checked at 1e-4 by the parity tests).  Storage: lower triangle of A in rows 0..n-1, the right-hand
-// side as ROW n -- eliminating it like any other row leaves w = D^-1 L^-1 b there, the right-hand
-// side of the back substitution L^T x = w.  Right-looking, 16 columns per panel:
-//   A  wave 0 factors the 16x16 diagonal block in registers (lane = row, pivot rows broadcast with
-//      v_readlane) and publishes U11 and the reciprocal pivots;
-//   B  one thread per remaining row eliminates its 16 panel entries against U11 (broadcast LDS
-//      reads), keeps the multipliers in place and the unscaled entries d_j l_ij as W^T;
-//   C  trailing update A22 -= L21 W (lower triangle + rhs row), one 4x4 register tile per thread.
-// 3 barriers per panel instead of one per column, and no redundant upper-triangle work.
-// --------------------------------------------------------------------------------------
-constexpr int kPanel = 16;
-
-__host__ __device__ inline int ldlt_ld(int n) {  // row stride: >= round16(n), odd multiple of 4 (conflict-free b128 by row)
-  int ld = ((n + 15) & ~15) + 4;
-  while ((ld & 7) != 4) ld += 4;
-  return ld;
-}
-__host__ __device__ inline int ldlt_ldw(int n) { return ((n + 1 + 3) & ~3) + 4; }   // W^T row stride
-__host__ __device__ inline int solve_scratch_floats(int P) {   // MLP partials (4096) or the LDL^T scratch, whichever is larger
-  const int need = P >= 32 ? kPanel * ldlt_ldw(P) + 288 : 0;
-  return need > 4096 ? ((need + 3) & ~3) : 4096;
-}
-__host__ __device__ inline size_t solve_big_floats(int P) { return (size_t)(P + 4) * ldlt_ld(P); }
-
-__device__ __forceinline__ float rdlane(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-
-__device__ __attribute__((always_inline)) void ldlt_solve_blocked(float* A, int ld, int n, float* x,
-                                                                  float* scratch /* >= 16*ldw + 272 floats */) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int m = n + 1;                 // rows including the right-hand side
-  const int ldw = ldlt_ldw(n);
-  float* sWT = scratch;                // [16][ldw]
-  float* sU = sWT + kPanel * ldw;      // [16][16]  upper part of the factored diagonal block
-  float* sDinv = sU + kPanel * kPanel; // [16]
-#ifdef BANET_TIMING
-  __shared__ float sDbg[4];
-  float dA = 0.f, dB = 0.f, dC = 0.f;
-#endif
-  for (int k0 = 0; k0 < n; k0 += kPanel) {
-    const int nb = min(kPanel, n - k0);
-    STICK(pa);
-    // ---- A: diagonal block (wave 0) ------------------------------------------------------
-    if (tid < 64) {
-      const int row = lane & 15;
-      float a[kPanel];
-#pragma unroll
-      for (int c = 0; c < kPanel; ++c) {
-        const bool in = row < nb && c < nb;
-        const int r = k0 + row, cc = k0 + c;
-        const int idx = in ? (c <= row ? r * ld + cc : cc * ld + r) : 0;   // symmetric read from the lower triangle
-        const float v = A[idx];
-        a[c] = in ? v : (c == row ? 1.f : 0.f);                          // identity padding of a partial panel
-      }
-      float myinv = 1.f;
-#pragma unroll
-      for (int j = 0; j < kPanel; ++j) {
-        // pivot row j: all broadcasts first, then the arithmetic (a v_readlane feeding the very next VALU instruction costs
-        // wait states; batched, the 16 - j reads pipeline)
-        float pr[kPanel];
-#pragma unroll
-        for (int c = j; c < kPanel; ++c) pr[c] = rdlane(a[c], j);
-        __builtin_amdgcn_sched_barrier(0);
-        const float inv = __builtin_amdgcn_rcpf(pr[j]);                  // v_rcp_f32: <= 1 ulp
-        if (row == j) myinv = inv;
-        const float l = row > j ? a[j] * inv : 0.f;
-#pragma unroll
-        for (int c = j + 1; c < kPanel; ++c) a[c] = fmaf(-l, pr[c], a[c]);
-        a[j] = row > j ? l : a[j];
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (lane < kPanel) {
-        sDinv[row] = myinv;
-#pragma unroll
-        for (int c = 0; c < kPanel; ++c) {
-          if (c <= row) {
-            if (row < nb && c < nb) A[(k0 + row) * ld + k0 + c] = a[c];
-          } else {
-            sU[row * kPanel + c] = a[c];
-          }
-        }
-      }
-    }
-    __syncthreads();
-    STICK(pb);
-    // ---- B: panel rows below the block ---------------------------------------------------
-    const int base = k0 + nb, mrem = m - base;
-    for (int t = tid; t < mrem; t += kSolveThreads) {
-      float* rowp = A + (base + t) * ld + k0;
-      float a[kPanel];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(rowp + 4 * q);
-        a[4 * q + 0] = (4 * q + 0 < nb) ? v.x : 0.f;
-        a[4 * q + 1] = (4 * q + 1 < nb) ? v.y : 0.f;
-        a[4 * q + 2] = (4 * q + 2 < nb) ? v.z : 0.f;
-        a[4 * q + 3] = (4 * q + 3 < nb) ? v.w : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < kPanel; ++j) {
-        sWT[j * ldw + t] = a[j];                        // d_j l_ij
-        const float l = a[j] * sDinv[j];
-        a[j] = l;
-#pragma unroll
-        for (int c = j + 1; c < kPanel; ++c) a[c] = fmaf(-l, sU[j * kPanel + c], a[c]);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<float4*>(rowp + 4 * q) = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
-    }
-    __syncthreads();
-    STICK(pc);
-    // ---- C: trailing update, 4x4 tiles of the lower triangle ---------------------------------
-    const int mt = (mrem + 3) >> 2, ntiles = mt * (mt + 1) / 2;
-    for (int t = tid; t < ntiles; t += kSolveThreads) {
-      int I4 = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-      while ((I4 + 1) * (I4 + 2) / 2 <= t) ++I4;
-      while (I4 * (I4 + 1) / 2 > t) --I4;
-      const int C4 = t - I4 * (I4 + 1) / 2;
-      float acc[4][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
-      const float* Lp = A + (base + 4 * I4) * ld + k0;
-      const float* Wp = sWT + 4 * C4;
-#pragma unroll
-      for (int j4 = 0; j4 < 4; ++j4) {
-        float4 Lr[4], Wj[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Lr[r] = *reinterpret_cast<const float4*>(Lp + r * ld + 4 * j4);
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) Wj[jj] = *reinterpret_cast<const float4*>(Wp + (4 * j4 + jj) * ldw);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float lr[4] = {Lr[r].x, Lr[r].y, Lr[r].z, Lr[r].w};
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            acc[r][0] = fmaf(lr[jj], Wj[jj].x, acc[r][0]);
-            acc[r][1] = fmaf(lr[jj], Wj[jj].y, acc[r][1]);
-            acc[r][2] = fmaf(lr[jj], Wj[jj].z, acc[r][2]);
-            acc[r][3] = fmaf(lr[jj], Wj[jj].w, acc[r][3]);
-          }
-        }
-      }
-      float* Cp = A + (base + 4 * I4) * ld + base + 4 * C4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float4 cv = *reinterpret_cast<float4*>(Cp + r * ld);
-        cv.x -= acc[r][0];
-        cv.y -= acc[r][1];
-        cv.z -= acc[r][2];
-        cv.w -= acc[r][3];
-        *reinterpret_cast<float4*>(Cp + r * ld) = cv;
-      }
-    }
-    __syncthreads();
-#ifdef BANET_TIMING
-    {
-      STICK(pd);
-      dA += (float)(pb - pa);
-      dB += (float)(pc - pb);
-      dC += (float)(pd - pc);
-    }
-#endif
-  }
-  STICK(pe);
-  // ---- back substitution L^T x = w (wave 0), panels from the last to the first ---------------
-  if (tid < 64) {
-    const int li = lane & 15, part = lane >> 4;
-    const int npan = (n + kPanel - 1) / kPanel;
-    for (int p = npan - 1; p >= 0; --p) {
-      const int k0 = p * kPanel, nb = min(kPanel, n - k0), base = k0 + nb;
-      // t_l = w_l - sum_{j >= base} L[j][k0 + l] x_j : 4 interleaved slices of j, one per 16-lane row
-      float tsum = 0.f;
-      {
-        const float* Lc = A + k0 + (li < nb ? li : 0);
-        float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
-        int j = base + part;
-        for (; j + 12 < n; j += 16) {   // 4 independent loads in flight per lane
-          const float l0 = Lc[j * ld], l1 = Lc[(j + 4) * ld], l2 = Lc[(j + 8) * ld], l3 = Lc[(j + 12) * ld];
-          t0 = fmaf(l0, x[j], t0);
-          t1 = fmaf(l1, x[j + 4], t1);
-          t2 = fmaf(l2, x[j + 8], t2);
-          t3 = fmaf(l3, x[j + 12], t3);
-        }
-        for (; j < n; j += 4) t0 = fmaf(Lc[j * ld], x[j], t0);
-        tsum = li < nb ? (t0 + t1) + (t2 + t3) : 0.f;
-      }
-      tsum += __shfl_xor(tsum, 16, 64);
-      tsum += __shfl_xor(tsum, 32, 64);
-      float tl = (li < nb ? A[n * ld + k0 + li] : 0.f) - tsum;
-      float col[kPanel];   // column l of the block's unit lower triangle: L[k0 + i][k0 + l], i > l
-#pragma unroll
-      for (int i = 0; i < kPanel; ++i) col[i] = (i > li && i < nb) ? A[(k0 + i) * ld + k0 + li] : 0.f;
-#pragma unroll
-      for (int i = kPanel - 1; i >= 1; --i) {
-        const float xi = rdlane(tl, i);      // final once rows > i have been applied
-        tl = fmaf(-col[i], xi, tl);
-      }
-      if (lane < nb) x[k0 + lane] = tl;
-    }
-  }
-  __syncthreads();
-#ifdef BANET_TIMING
-  {
-    STICK(pf);
-    if (tid == 0) {
-      sDbg[0] = dA;
-      sDbg[1] = dB;
-      sDbg[2] = dC;
-      sDbg[3] = (float)(pf - pe);
-      x[n + 0] = dA; x[n + 1] = dB; x[n + 2] = dC; x[n + 3] = (float)(pf - pe);
-    }
-    __syncthreads();
-  }
-#endif
-}
-
 __device__ void rodrigues(const float w[3], bool clamp, float Rw[9], float V[9]) {
   // exp(w): bundlenet.py:17-37 / legacy/ba.py:60-80 ; V(w): bundlenet.py:39-46
   const float th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
@@ -562,25 +289,6 @@ __device__ void rodrigues(const float w[3], bool clamp, float Rw[9], float V[9])
 constexpr int kPcgMaxIt = 40;
 constexpr float kPcgTol2 = 2.5e-14f;     // (1.6e-7)^2 on |r|^2 / |b|^2
 constexpr float kPcgMinSchur = 1.f / 4096.f;   // smallest Schur complement of the undamped coefficient, relative to a_PP, that CG + Schur keeps
-
-// block-wide sums of NV values per thread (fixed order); sr: 16 * NV floats, a different buffer than the previous call's
-template <int NV>
-__device__ __forceinline__ void block_sum_n(float (&v)[NV], float* sr) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const float t = wave_sum_fast(v[k]);
-    if (lane == 0) sr[wv * NV + k] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < kSolveWaves; ++i) t += sr[i * NV + k];
-    v[k] = t;
-  }
-}
 
 __device__ bool pcg_schur_solve(const float* A, int ld, int n, bool undamped_last, float* x, float* scratch) {
   const int tid = threadIdx.x;
@@ -693,22 +401,23 @@ __global__ __launch_bounds__(kSolveThreads) void ba_solve_update_kernel(const So
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int P = a.P, C = a.C, K = a.K;
-  const bool blocked = P >= kGrid;                   // bundle variants: blocked LDL^T, rhs stored as row P
-  const int ld = blocked ? ldlt_ld(P) : P + 2;
-  const int arows = blocked ? P + 4 : P;
+  const SolvePlan& pl = a.pl;                        // layout, strides and method: plan_solve (solve_plan.hpp)
+  const int method = pl.method;
+  const bool blocked = solve_method_blocked(method); // bundle variants: blocked LDL^T, rhs stored as row P
+  const int ld = pl.ld;
   // P too large for an LDS-resident matrix (K = 256 windows: P up to 6*7 + 256): the matrix lives in the caller's
   // workspace (L2-resident, 370 KB per window) and only the vectors / scratch stay in LDS.  Same code, global pointer.
   constexpr bool big = BIG;
-  float* gA = big ? a.bigA + (size_t)b * solve_big_floats(P) : nullptr;
-  float* sA = smem;                 // [arows][ld] augmented (unused when big)
-  float* sX = sA + (big ? 0 : ((arows * ld + 3) & ~3));  // [P]  (every carve offset a multiple of 4 floats: float4 LDS accesses)
-  float* sH0 = sX + ((P + 3) & ~3); // MLP ping
-  float* sH1 = sH0 + 4 * C;         // MLP pong
-  float* sAvg = sH1 + 4 * C;        // [C]
-  float* sRed = sAvg + ((C + 3) & ~3);  // [8]
-  float* sScal = sRed + 20;         // pivot reciprocal, -, flags
-  float* sPart = sRed + 24;         // [solve_scratch_floats(P)] MLP partial sums / solver scratch
-  int* sPerm = reinterpret_cast<int*>(sPart + solve_scratch_floats(P));  // [P]
+  float* gA = big ? a.bigA + (size_t)b * pl.big_floats : nullptr;
+  float* sA = smem + pl.off_A;      // [arows][ld] augmented (absent when big)
+  float* sX = smem + pl.off_X;      // [P]
+  float* sH0 = smem + pl.off_H0;    // MLP ping
+  float* sH1 = smem + pl.off_H1;    // MLP pong
+  float* sAvg = smem + pl.off_Avg;  // [C]
+  float* sRed = smem + pl.off_Red;  // block_sum's per-wave values
+  float* sScal = smem + pl.off_Scal;  // pivot index, pivot reciprocal, the accept / terminate flag
+  float* sPart = smem + pl.off_Part;  // MLP partial sums / solver scratch
+  int* sPerm = reinterpret_cast<int*>(smem + pl.off_Perm);  // [P]
 
   LmCtl* ctl = a.ctl ? a.ctl + b : nullptr;
   if (ctl && ctl->active == 0) return;
@@ -796,31 +505,28 @@ __global__ __launch_bounds__(kSolveThreads) void ba_solve_update_kernel(const So
   __syncthreads();
   STICK(tk2);
   // ---- solve --------------------------------------------------------------------------
-  if (legacy && P == 6) {
+  if (method == kSolveQr6 || method == kSolveInverse6) {   // the legacy 6 x 6 system, on thread 0
     if (tid == 0) {
       float rhs[6];
       for (int i = 0; i < 6; ++i) rhs[i] = sA[i * ld + P];
-      if (a.lm.solver == BANET_SOLVER_INVERSE)
+      if (method == kSolveInverse6)
         inverse_solve_small(sA, ld, rhs, sX);     // `qr = False`, legacy/ba.py:203,290
       else
-        qr_solve_small(sA, ld, rhs, 6, sX);
+        qr_solve_small(sA, ld, rhs, sX);
     }
     __syncthreads();
   } else {
-    float* sCol = sPart;                // the MLP scratch is free by now (4096 floats)
-    if (P <= kGrid - 1) {               // pose-only variants: pivoted LU as tf.matrix_solve
+    float* sCol = sPart;                // the MLP scratch is free by now
+    if (method == kSolveLu) {           // pose-only variants: pivoted LU as tf.matrix_solve
       lu_solve_regs<1>(sA, ld, P, sX, sPerm, sCol, sCol + 2 * kGrid, reinterpret_cast<int*>(sCol + 3 * kGrid), sScal);
     } else if constexpr (big) {
-      ldlt_solve_blocked(gA, ld, P, sX, sCol);    // matrix in global memory (workgroup-private, L2)
+      ldlt_solve_blocked(gA, ld, pl.ldw, P, sX, sCol);    // matrix in global memory (workgroup-private, L2)
     } else {
       // matrix in LDS: conjugate gradients on the damped block first (reads the matrix only), the LDL^T when they do not
-      // converge (kDevSolveLdltOnly: LDL^T only, A/B and parity tests)
+      // converge; kSolveLdlt: the LDL^T alone (kDevSolveLdltOnly, or a system the conjugate gradients have no room for)
       bool cg_ok = false;
-      // pcg_schur_solve covers 4 threads per row and needs 2 n1p + 8 kSolveWaves floats of scratch: larger systems (none is
-      // LDS-resident today: solve_lds_bytes stops at P ~ 190) go straight to the factorisation instead of dropping rows
-      const bool cg_fits = 4 * P <= kSolveThreads && 2 * ((P + 3) & ~3) + 8 * kSolveWaves <= solve_scratch_floats(P);
-      if (cg_fits && !(a.flags & kDevSolveLdltOnly)) cg_ok = pcg_schur_solve(smem, ld, P, a.variant == BANET_BUNDLE, sX, sCol);
-      if (!cg_ok) ldlt_solve_blocked(smem, ld, P, sX, sCol);
+      if (method == kSolveCgLdlt) cg_ok = pcg_schur_solve(sA, ld, P, a.variant == BANET_BUNDLE, sX, sCol);
+      if (!cg_ok) ldlt_solve_blocked(sA, ld, pl.ldw, P, sX, sCol);
     }
   }
   STICK(tk3);
@@ -891,76 +597,11 @@ __global__ void zero_iters_kernel(int32_t* iters, int B) {
   if (b < B) iters[b] = 0;
 }
 
-size_t solve_lds_bytes(int P, int C, bool big) {
-  const bool blocked = P >= kGrid;
-  const int ld = blocked ? ldlt_ld(P) : P + 2, arows = blocked ? P + 4 : P;
-  const size_t fl = (size_t)(big ? 0 : ((arows * ld + 3) & ~3)) + ((P + 3) & ~3) + 8 * C + ((C + 3) & ~3) + 24 +
-                    solve_scratch_floats(P) + P + 8;
-  return fl * sizeof(float);
-}
-
-// bytes of caller workspace the solve needs for its matrix (0: it fits in LDS)
-size_t solve_big_bytes(int B, int P, int C) {
-  if (solve_lds_bytes(P, C, false) <= 160 * 1024) return 0;
-  return (size_t)B * solve_big_floats(P) * sizeof(float);
-}
-
+// a.pl: a plan that plan_solve accepted; a.bigA: a.B * a.pl.big_floats floats where a.pl.big (the callers in api.hip check both)
 int launch_solve(const SolveArgs& a, hipStream_t s) {
-  const bool need_big = solve_lds_bytes(a.P, a.C, false) > 160 * 1024;
-  if (need_big && a.bigA == nullptr) return BANET_ERR_UNSUPPORTED;   // only banet_lm_level_f32 has a workspace for it
-  const size_t lds = solve_lds_bytes(a.P, a.C, need_big);
-  if (lds > 160 * 1024) return BANET_ERR_UNSUPPORTED;
-  if (need_big) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)ba_solve_update_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ba_solve_update_kernel<true>, dim3(a.B), dim3(kSolveThreads), lds, s, a);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)ba_solve_update_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ba_solve_update_kernel<false>, dim3(a.B), dim3(kSolveThreads), lds, s, a);
-  }
-  return hipGetLastError() == hipSuccess ? BANET_OK : BANET_ERR_LAUNCH;
-}
-
-// --------------------------------------------------------------------------------------
-// banet_spd_solve_f32: x = A^-1 b for B symmetric positive definite systems (32 <= P <= ~190), the blocked LDL^T of the
-// update kernel as an op of its own.  Used by the backward of the dense layer (banet_amd/dense_train.py): the forward
-// solution of the damped system is recomputed and the implicit-function gradient lam = A^-T g is a second call with the
-// same matrix -- torch.linalg.solve costs ~2 ms per iteration there (rocSOLVER getrf + per-item trsv launches).
-// --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kSolveThreads) void spd_solve_kernel(const float* __restrict__ A, const float* __restrict__ rhs,
-                                                                  float* __restrict__ x, int P) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int ld = ldlt_ld(P);
-  float* sA = smem;                                   // [(P + 4)][ld], right-hand side as row P
-  float* sX = sA + (((P + 4) * ld + 3) & ~3);         // [P + 8]
-  float* sScr = sX + ((P + 8 + 3) & ~3);              // [solve_scratch_floats(P)]
-  const float* A_g = A + (size_t)b * P * P;
-  for (int e = tid; e < P * P; e += kSolveThreads) {
-    const int i = e / P, j = e - i * P;
-    sA[i * ld + j] = A_g[e];
-  }
-  for (int i = tid; i < P; i += kSolveThreads) sA[P * ld + i] = rhs[(size_t)b * P + i];
-  __syncthreads();
-  ldlt_solve_blocked(smem, ld, P, sX, sScr);
-  for (int k = tid; k < P; k += kSolveThreads) x[(size_t)b * P + k] = sX[k];
-}
-
-static size_t spd_solve_lds_bytes(int P) {
-  const size_t fl = (size_t)(((P + 4) * ldlt_ld(P) + 3) & ~3) + ((P + 8 + 3) & ~3) + (size_t)solve_scratch_floats(P);
-  return fl * sizeof(float);
-}
-
-bool spd_solve_fits(int P) { return P >= kGrid && spd_solve_lds_bytes(P) <= 160 * 1024; }
-
-int launch_spd_solve(const float* A, const float* rhs, float* x, int B, int P, hipStream_t s) {
-  if (P < kGrid) return BANET_ERR_UNSUPPORTED;                 // the blocked factorisation wants at least two panels
-  const size_t lds = spd_solve_lds_bytes(P);
-  if (lds > 160 * 1024) return BANET_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)spd_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(spd_solve_kernel, dim3(B), dim3(kSolveThreads), lds, s, A, rhs, x, P);
+  const auto kernel = a.pl.big ? ba_solve_update_kernel<true> : ba_solve_update_kernel<false>;
+  if (a.pl.lds_attr) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.pl.lds);
+  hipLaunchKernelGGL(kernel, dim3(a.B), dim3(kSolveThreads), a.pl.lds, s, a);
   return hipGetLastError() == hipSuccess ? BANET_OK : BANET_ERR_LAUNCH;
 }
 

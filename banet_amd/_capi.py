@@ -180,6 +180,13 @@ class PosePrior(ctypes.Structure):
     _fields_ = [("R0", _FP), ("T0", _FP), ("Lambda", _FP), ("scale", ctypes.c_float), ("reserved_", ctypes.c_int32)]
 
 
+class PosePriorGrad(ctypes.Structure):
+    """mirror of banet_pose_prior_grad_t (banet_pose_prior_add_grad_f32: every pointer optional, at least one; reserved_ = 0)"""
+    _fields_ = [("gR", _FP), ("gT", _FP), ("gR0", _FP), ("gT0", _FP), ("gLambda", _FP), ("gscale", _FP), ("flags", ctypes.c_int32),
+                ("reserved_", ctypes.c_int32)]
+
+
+POSE_PRIOR_GRAD_OVERWRITE_STATE, POSE_PRIOR_GRAD_OVERWRITE_PRIOR = 1, 2  # banet_hip.h: BANET_POSE_PRIOR_GRAD_OVERWRITE_STATE / _PRIOR
 PRIOR_GRAD_OVERWRITE, PRIOR_GRAD_ACCUMULATE = 1, 2  # banet_hip.h: BANET_PRIOR_GRAD_OVERWRITE / _ACCUMULATE
 
 ADJOINT_OVERWRITE, ADJOINT_OVERWRITE_MAP = 1, 2  # banet_hip.h: BANET_ADJOINT_OVERWRITE / _OVERWRITE_MAP
@@ -247,6 +254,8 @@ EXPORTS = {
     "banet_prior_terms_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Prior), ctypes.POINTER(PriorGradIn),
                                                   ctypes.POINTER(PriorGradOut), _FP, ctypes.c_size_t, _FP]),
     "banet_pose_prior_apply_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(PosePrior)] + [_FP] * 4 + [_FP]),
+    "banet_pose_prior_add_grad_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(PosePrior)] + [_FP] * 4 +
+                                      [ctypes.POINTER(PosePriorGrad), _FP]),
     "banet_lm_level_pose_prior_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Level), ctypes.POINTER(Prior), ctypes.POINTER(PosePrior)]),
     "banet_lm_level_pose_prior_f32": (ctypes.c_int, [ctypes.POINTER(Level), ctypes.POINTER(Mlp), ctypes.c_float, ctypes.c_int,
                                                      ctypes.POINTER(LmParams), ctypes.POINTER(Prior), ctypes.POINTER(PosePrior),

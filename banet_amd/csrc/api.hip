@@ -553,6 +553,15 @@ int banet_lm_level_pose_prior_f32(const banet_level_t* lv, const banet_mlp_t* ml
   return lm_level_enqueue(run, static_cast<hipStream_t>(stream));
 }
 
+int banet_pose_prior_add_grad_f32(const banet_level_t* lv, const banet_pose_prior_t* pp, const float* R, const float* T,
+                                  const float* gAtA, const float* gAtb, const banet_pose_prior_grad_t* out, banet_stream_t stream) {
+  if (!R || !T || !gAtA || !gAtb) return BANET_ERR_INVALID_ARG;
+  PosePriorGradPlan pl;
+  const int rc = plan_pose_prior_grad(lv, pp, out, &pl);
+  if (rc != BANET_OK) return rc;
+  return launch_pose_prior_grad(pl, *pp, R, T, gAtA, gAtb, *out, static_cast<hipStream_t>(stream));
+}
+
 int banet_resample_f32(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,
                        banet_stream_t stream) {
   if (!data || !warp || !out) return BANET_ERR_INVALID_ARG;

@@ -5,6 +5,7 @@
 #include "prior_plan.hpp"  // the prior term's regions and the Gram pass's partial rows (host-only like plan.hpp)
 #include "prior_grad_plan.hpp"  // its backward: outputs, per-pixel grid, Gh / gh regions (host-only like plan.hpp)
 #include "pose_prior_plan.hpp"  // the pose prior: struct checks, the empty test, the grid (host-only like plan.hpp)
+#include "pose_prior_grad_plan.hpp"  // its backward: checks, grid, the phases per output set (host-only like plan.hpp)
 #include "solve_plan.hpp"  // the solve: method, LDS-or-workspace switch, LDS layout (host-only like plan.hpp)
 
 namespace banet {
@@ -156,6 +157,9 @@ struct PosePriorRun {   // a planned pose prior next to its pointers; host memor
   banet_pose_prior_t pp;
 };
 int launch_pose_prior_add(const PosePriorRun& run, const float* R, const float* T, float* AtA, float* Atb, hipStream_t s);   // every iteration
+// ---- pose_prior_grad.hip: its backward, one launch per iteration (banet_pose_prior_add_grad_f32; plan: pose_prior_grad_plan.hpp) ----
+int launch_pose_prior_grad(const PosePriorGradPlan& pl, const banet_pose_prior_t& pp, const float* R, const float* T, const float* gAtA,
+                           const float* gAtb, const banet_pose_prior_grad_t& out, hipStream_t s);
 
 // ---- prep.hip --------------------------------------------------------------------------
 int launch_resample(const float* data, const float* warp, float* out, int B, int N, int C, int H, int W, int mode,

@@ -234,7 +234,7 @@ class DenseBA:
                 depth_outputs.append(ops.depth_output(prob.keep[2], prob.keep[3], st.Wc).reshape(self.levels[li].depth.shape))
         return st, counts
 
-    def solve_differentiable(self, iters_per_level, R=None, T=None, Wc=None, outputs=None, prior=None):
+    def solve_differentiable(self, iters_per_level, R=None, T=None, Wc=None, outputs=None, prior=None, pose_prior_backward=False):
         """The same fixed-count schedule attached to the autograd graph: gradients flow to the levels' src / tgt / depth /
         basis tensors, to the initial (R, T, Wc) and to the lambda weights through the fused backward kernels
         (banet_amd/dense_train.py, csrc/adjoint.hip; the reference differentiates bundlenet.py:376-397 with tf.gradients +
@@ -242,10 +242,12 @@ class DenseBA:
         windows.  outputs: a list that receives (R, T, Wc) after each level, attached to the graph.  prior: a DensePrior as in
         solve(prior=) (`bundle` only, K >= 1); its tensors may require grad -- a learned obs_depth / obs_weight, the (Lambda, eta) of
         transfer_prior -- and the levels' depth and basis receive the term's gradient as well.  None or empty: today's launches.
-        A prior with pose=: NotImplementedError (the pose prior has no backward yet)."""
+        A prior with pose=: NotImplementedError unless pose_prior_backward=True, which differentiates through the pose prior as well
+        (gradients reach R0, T0 and Lambda; `bundle`, and with a pose prior alone also `bundle_camera`); the default keeps the
+        earlier refusal until a later change flips it."""
         from . import dense_train
         return dense_train.solve_differentiable(self, self.levels, self.lambda_weights, iters_per_level, R, T, Wc, outputs=outputs,
-                                                prior=prior)
+                                                prior=prior, pose_prior_backward=pose_prior_backward)
 
     def step_from(self, level_index, R, T, Wc=None):
         """ONE iteration of level `level_index` from the given state -> (state after it; .delta / .lambda_out hold the

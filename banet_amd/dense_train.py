@@ -388,9 +388,11 @@ class _LevelSolve(torch.autograd.Function):
         return (None, None, None) + _level_backward(ctx, gR, gT, gW)
 
 
-def _level_backward(ctx, gR, gT, gW, prior=None, Le=None, prior_want=()):
+def _level_backward(ctx, gR, gT, gW, prior=None, Le=None, prior_want=(), pose_prior=None, pose_want=()):
     """The backward of a level's iterations -> (dsrc, dtgt, ddepth, dbasis, gR, gT, gW, *glayers), and with a prior (the level's
-    ops.Prior, its terms Le, the prior outputs some input needs) the ops.PriorGrad behind them.  Without one: _LevelSolve's launches."""
+    ops.Prior, its terms Le, the prior outputs some input needs) the ops.PriorGrad behind them.  Without one: _LevelSolve's launches.
+    With a pose prior (the level's ops.PosePrior, and which of gR0 / gT0 / gLambda some input needs): one
+    banet_pose_prior_add_grad_f32 per iteration after the small step, and the result is (res, pg, {gR0, gT0, gLambda})."""
     ba, li = ctx.ba, ctx.li
     prob = ba.problems[li]
     pairs = prob.pairs
@@ -422,6 +424,7 @@ def _level_backward(ctx, gR, gT, gW, prior=None, Le=None, prior_want=()):
         if SmallStepHip.supported(ba.variant, B, N, C, K, pairs, dev) else None
     glayers = None if hip_small is not None else [torch.zeros_like(t) for t in flat]
     gLe = gee = None
+    pose_acc = {}
     for Ri, Ti, Wi, AtA, Atb, absres, delta in reversed(ctx.saved):
         Rv, Tv = Ri.reshape(B, pairs, 3, 3), Ti.reshape(B, pairs, 3, 1)
         if hip_small is not None:       # four launches; the lambda-weight gradients accumulate on the device
@@ -436,6 +439,13 @@ def _level_backward(ctx, gR, gT, gW, prior=None, Le=None, prior_want=()):
             gR, gT, gW = dR.reshape(B, pairs, 3, 3).clone(), dT.reshape(B, pairs, 3, 1).clone(), dW.reshape(B, K, 1).clone()
         if prior is not None:       # gAtA / gAtb are the post-prior matrices' and pass through; gLe / gee accumulate, gW -= Le^T gAtb
             gLe, gee, _ = ops.prior_add_grad(prob, Le, Wi, capi.f32c(gAtA), capi.f32c(gAtb), gLe, gee, gWc=gW.view(B, K))
+        if pose_prior is not None:  # the same matrices' gradients: gR / gT of this iteration += in place; gR0 / gT0 / gLambda accumulate
+            gR, gT = gR.contiguous(), gT.contiguous()     # over the level's iterations (written by the first call, added to after)
+            into = dict(gR=gR, gT=gT)
+            into.update(pose_acc)
+            got = ops.pose_prior_add_grad(prob, pose_prior, Ri, Ti, capi.f32c(gAtA), capi.f32c(gAtb), want=("gR", "gT") + tuple(pose_want),
+                                          into=into, overwrite=dict(state=False, prior=not pose_acc))
+            pose_acc = {n: getattr(got, n) for n in pose_want}
         for i in range(pairs):
             if pairs == 1:
                 gA_i, gb_i = gAtA, gAtb
@@ -472,6 +482,8 @@ def _level_backward(ctx, gR, gT, gW, prior=None, Le=None, prior_want=()):
     s_src, s_tgt, s_dep, s_bas, s_R, s_T = ctx.shapes
     res = (dsrc.reshape(s_src), dtgt.reshape(s_tgt), ddepth.reshape(s_dep),
            None if s_bas is None else dbasis.reshape(s_bas), gR.reshape(s_R), gT.reshape(s_T), gW) + tuple(glayers)
+    if pose_prior is not None:
+        return res, pg, pose_acc
     return res if prior is None else (res, pg)
 
 
@@ -512,6 +524,55 @@ class _LevelSolvePrior(torch.autograd.Function):
         res, pg = _level_backward(ctx, gR, gT, gW, ctx.prior, ctx.Le, want)
         gp = [None if (pg is None or n not in want) else getattr(pg, n).reshape(s) for n, s in zip(names, ctx.pshapes)]
         return (None, None, None, None) + res[:7] + tuple(gp) + res[7:]
+
+
+class _LevelSolvePosePrior(torch.autograd.Function):
+    """All fixed-count iterations of one pyramid level with an ops.PosePrior, and an ops.Prior as well or None: between assembly and
+    solve of every iteration the coefficient prior's step (as _LevelSolvePrior) and then the pose prior's at that iteration's R, T --
+    the order and the bits of ops.lm_level(prior=, pose_prior=) -- and the POST-prior AtA / Atb are what the small step's backward
+    is given.  The backward calls banet_pose_prior_add_grad_f32 once per iteration, after the small step (and after
+    banet_prior_add_grad_f32) and before the dense adjoint.  R0, T0 and Lambda enter as inputs: autograd sums them over the levels."""
+
+    @staticmethod
+    def forward(ctx, ba, li, n_iter, prior, pose_prior, src, tgt, depth, basis, R, T, Wc, Lambda, eta, obs, weight, pR0, pT0, pLambda,
+                *flat_layers):
+        prob, mlp = ba.problems[li], ba.mlps[li]
+        pairs = prob.pairs
+        st = ops.LmState(R.detach(), T.detach(), Wc.detach(), P=6 * pairs + ba.K, pairs=pairs)
+        Le = unit = None
+        if prior is not None:
+            Le, ee = ops.prior_terms(prob, prior)
+            unit = ops.Prior(Lambda=Le, eta=ee, scale=1.0)
+        saved = []
+        sws = pws = None
+        for _ in range(n_iter):
+            Ri, Ti, Wi = st.R.clone(), st.T.clone(), st.Wc.clone()
+            AtA, Atb, absres, nvalid = ops.ba_assemble(prob, st.R, st.T, st.Wc)
+            if unit is not None:
+                pws = ops.prior_apply(prob, unit, st.Wc, AtA, Atb, pws)
+            ops.pose_prior_apply(prob, pose_prior, st.R, st.T, AtA, Atb)
+            sws = ops.ba_solve_update(prob, mlp, ba.l2_base, AtA, Atb, absres, nvalid, st, sws)
+            saved.append((Ri, Ti, Wi, AtA, Atb, absres, st.delta.clone()))
+        ctx.ba, ctx.li, ctx.saved = ba, li, saved
+        ctx.mlp = mlp
+        ctx.layers = flat_layers
+        ctx.prior, ctx.Le, ctx.pose_prior = prior, Le, pose_prior
+        ctx.shapes = (src.shape, tgt.shape, depth.shape, None if basis is None else basis.shape, R.shape, T.shape)
+        ctx.pshapes = [None if x is None else x.shape for x in (Lambda, eta, obs, weight)]
+        ctx.ppshapes = [x.shape for x in (pR0, pT0, pLambda)]
+        return st.R.clone().reshape(R.shape), st.T.clone().reshape(T.shape), st.Wc.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gR, gT, gW):
+        names = ("gLambda", "geta", "gobs", "gweight")
+        want = tuple(n for n, k, s in zip(names, ctx.needs_input_grad[12:16], ctx.pshapes) if k and s is not None)
+        pnames = ("gR0", "gT0", "gLambda")
+        pwant = tuple(n for n, k in zip(pnames, ctx.needs_input_grad[16:19]) if k)
+        res, pg, pacc = _level_backward(ctx, gR, gT, gW, ctx.prior, ctx.Le, want, ctx.pose_prior, pwant)
+        gp = [None if (pg is None or n not in want) else getattr(pg, n).reshape(s) for n, s in zip(names, ctx.pshapes)]
+        gpp = [None if n not in pacc else pacc[n].reshape(s) for n, s in zip(pnames, ctx.ppshapes)]
+        return (None, None, None, None, None) + res[:7] + tuple(gp) + tuple(gpp) + res[7:]
 
 
 class _AssembleDiff(torch.autograd.Function):
@@ -611,7 +672,8 @@ def depth_nll_loss(depth, depth_var, depth_gt, mask=None, var_floor=1e-12):
     return torch.where(keep, nll, torch.zeros_like(nll)).sum(1) / keep.sum(1).clamp(min=1)
 
 
-def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=None, Wc=None, outputs=None, prior=None):
+def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=None, Wc=None, outputs=None, prior=None,
+                         pose_prior_backward=False):
     """Differentiable DenseBA.solve with fixed iteration counts: `levels` = the DenseLevel objects `ba` was built from (their
     src / tgt / depth / basis tensors may require grad), `lambda_weights` = per level five (filters, biases) pairs (tensors
     that may require grad, or arrays).  Returns (R [B,3,3], T [B,3,1], Wc [B,K,1]) attached to the autograd graph
@@ -621,20 +683,35 @@ def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=
     prior: a dense.DensePrior whose tensors may require grad (coef = (Lambda, eta), each level's obs / weight): its term is added
     between assembly and solve of every iteration as DenseBA.solve(prior=) adds it, and gradients reach the prior's tensors, and
     through the term the levels' depth and basis (banet_prior_add_grad_f32 / banet_prior_terms_grad_f32).  `bundle` only, K >= 1.
-    None or an empty prior: the launches and bits of the call without the argument."""
+    None or an empty prior: the launches and bits of the call without the argument.
+    pose_prior_backward: a prior with pose=(R0, T0, Lambda) is differentiated through (banet_pose_prior_add_grad_f32): its term is
+    added after the coefficient prior's in every iteration, as DenseBA.solve(prior=) adds it, and gradients reach R0, T0 and Lambda
+    (R0 as nine free entries) and, through the term, the state.  `bundle` with or without a coefficient / observation prior, and
+    the pose-only `bundle_camera` with a pose prior alone.  The path is opt-in: with the default, False, a prior with pose= still
+    raises NotImplementedError, the refusal the callers of the earlier interface (and its tests) rely on; a later change flips
+    the default.  Without a pose prior, or with an empty one, the keyword changes nothing: the launches and bits without it."""
     if ba.variant not in ("bundle", "bundle_camera"):
         raise capi.BanetError("solve_differentiable: bundle / bundle_camera variants only")
-    priors = None
-    if prior is not None and getattr(prior, "pose", None) is not None:
-        raise NotImplementedError("solve_differentiable: the pose prior (DensePrior(pose=...)) has no backward yet -- the gradient of "
-                                  "banet_pose_prior_apply_f32 with respect to R, T, R0, T0 and Lambda is missing")
+    priors = pose_priors = None
+    has_pose = prior is not None and getattr(prior, "pose", None) is not None
+    if has_pose and not pose_prior_backward:
+        raise NotImplementedError("solve_differentiable: the pose prior (DensePrior(pose=...)) is differentiated through only on request -- "
+                                  "its backward (banet_pose_prior_add_grad_f32: the gradient with respect to R, T, R0, T0 and Lambda) runs "
+                                  "with pose_prior_backward=True")
     if prior is not None:
-        if ba.variant != "bundle" or ba.K < 1:
-            raise capi.BanetError("solve_differentiable: a prior needs the `bundle` variant with K >= 1")
         n = min(len(ba.problems), len(iters_per_level))
-        priors = prior.level_priors(ba.problems[:n])
-        if any(ops.prior_workspace_bytes(p, q) == 0 for p, q in zip(ba.problems[:n], priors) if not ops._prior_is_empty(q)):
-            raise capi.BanetError("solve_differentiable: the prior does not fit the levels")
+        pose_only = has_pose and prior.coef is None and prior.depth_obs is None
+        if not pose_only:
+            if ba.variant != "bundle" or ba.K < 1:
+                raise capi.BanetError("solve_differentiable: a prior needs the `bundle` variant with K >= 1")
+            priors = prior.level_priors(ba.problems[:n])
+            if any(ops.prior_workspace_bytes(p, q) == 0 for p, q in zip(ba.problems[:n], priors) if not ops._prior_is_empty(q)):
+                raise capi.BanetError("solve_differentiable: the prior does not fit the levels")
+        if has_pose:
+            pose_priors = prior.level_pose_priors(ba.problems[:n])
+            if any(ops.lm_level_workspace_bytes(p, None, q) == 0 for p, q in zip(ba.problems[:n], pose_priors)
+                   if not ops._pose_prior_is_empty(q)):
+                raise capi.BanetError("solve_differentiable: the pose prior does not fit the levels (up to 8 target frames)")
     dev = ba.intr.device
     B, K, pairs = ba.B, ba.K, ba.pairs
     if pairs == 1:
@@ -655,7 +732,13 @@ def solve_differentiable(ba, levels, lambda_weights, iters_per_level, R=None, T=
             flat += [w.reshape(w.shape[-2], w.shape[-1]), _to_param(b, dev).reshape(-1)]
         ba.mlps[li] = ops.MlpWeights([(flat[2 * i].detach(), flat[2 * i + 1].detach()) for i in range(5)], dev)
         pr = priors[li] if (priors is not None and li < len(priors)) else None
-        if ops._prior_is_empty(pr):
+        pp = pose_priors[li] if (pose_priors is not None and li < len(pose_priors)) else None
+        if not ops._pose_prior_is_empty(pp):
+            pr = None if ops._prior_is_empty(pr) else pr
+            ptens = (None,) * 4 if pr is None else (pr.Lambda, pr.eta, pr.obs_depth, pr.obs_weight)
+            R, T, Wc = _LevelSolvePosePrior.apply(ba, li, int(n_it), pr, pp, lv.src, lv.tgt, lv.depth, lv.basis, R, T, Wc, *ptens,
+                                                  pp.R0, pp.T0, pp.Lambda, *flat)
+        elif ops._prior_is_empty(pr):
             R, T, Wc = _LevelSolve.apply(ba, li, int(n_it), lv.src, lv.tgt, lv.depth, lv.basis, R, T, Wc, *flat)
         else:
             R, T, Wc = _LevelSolvePrior.apply(ba, li, int(n_it), pr, lv.src, lv.tgt, lv.depth, lv.basis, R, T, Wc, pr.Lambda, pr.eta,

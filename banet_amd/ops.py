@@ -975,6 +975,103 @@ def pose_prior_apply(level, pose_prior, R, T, AtA, Atb):
                                                      capi.ptr(R), capi.ptr(T), capi.ptr(AtA), capi.ptr(Atb), capi.stream()))
 
 
+POSE_PRIOR_GRAD_OUTPUTS = ("gR", "gT", "gR0", "gT0", "gLambda", "gscale")
+PosePriorGrad = collections.namedtuple("PosePriorGrad", POSE_PRIOR_GRAD_OUTPUTS)
+
+
+def pose_prior_add_grad(level, pose_prior, R, T, gAtA, gAtb, want=POSE_PRIOR_GRAD_OUTPUTS, into=None, overwrite=None):
+    """banet_pose_prior_add_grad_f32: the backward of one iteration's pose_prior_apply at the poses R [B,pairs,3,3], T [B,pairs,3].
+    gAtA [B,P,P], gAtb [B,P]: the gradients with respect to the post-prior matrices (they pass through to the assembly unchanged
+    and are not written) -> PosePriorGrad(gR [B,pairs,3,3], gT [B,pairs,3], gR0, gT0, gLambda [B,m,m], gscale [B]); the outputs not
+    named in `want` are None and are not computed.  into: {name: tensor} to write or accumulate into, in place; an output without
+    one is allocated and written.  overwrite: {"state": bool, "prior": bool} -- whether gR / gT and gR0 / gT0 / gLambda / gscale are
+    written or accumulated into (read-modify-write); default: written exactly where no output of the group comes from `into`.  An
+    output allocated here inside an accumulating group starts from zero.  A window's bits depend neither on the batch nor on `want`."""
+    lv = level.c
+    B, K, pairs = int(lv.B), int(lv.K), max(int(lv.pairs), 1)
+    m = 6 * pairs
+    P = m + K
+    unknown = [w for w in want if w not in POSE_PRIOR_GRAD_OUTPUTS]
+    if unknown:
+        raise capi.BanetError("pose_prior_add_grad: unknown outputs %s" % unknown)
+    if _pose_prior_is_empty(pose_prior):
+        raise capi.BanetError("pose_prior_add_grad: the empty pose prior has no backward")
+    pose_prior.check(B, int(lv.pairs))
+    for name, t, n in (("R", R, B * pairs * 9), ("T", T, B * pairs * 3), ("gAtA", gAtA, B * P * P), ("gAtb", gAtb, B * P)):
+        if t.numel() != n:
+            raise capi.BanetError("pose_prior_add_grad: %s must hold %d floats" % (name, n))
+    into = into or {}
+    groups = dict(gR="state", gT="state", gR0="prior", gT0="prior", gLambda="prior", gscale="prior")
+    ow = dict(state=not any(groups[n] == "state" and into.get(n) is not None for n in want),
+              prior=not any(groups[n] == "prior" and into.get(n) is not None for n in want))
+    ow.update(overwrite or {})
+    shapes = dict(gR=(B, pairs, 3, 3), gT=(B, pairs, 3), gR0=(B, pairs, 3, 3), gT0=(B, pairs, 3), gLambda=(B, m, m), gscale=(B,))
+    dev = gAtA.device
+    res, out = {}, capi.PosePriorGrad()
+    for name in POSE_PRIOR_GRAD_OUTPUTS:
+        t = None
+        if name in want:
+            t = into.get(name)
+            if t is None:
+                t = (torch.empty if ow[groups[name]] else torch.zeros)(shapes[name], dtype=torch.float32, device=dev)
+            elif t.numel() != int(torch.Size(shapes[name]).numel()):
+                raise capi.BanetError("pose_prior_add_grad: into[%r] must hold %s" % (name, shapes[name]))
+        res[name] = t
+        setattr(out, name, None if t is None else capi.ptr(t).value)
+    out.flags = (capi.POSE_PRIOR_GRAD_OVERWRITE_STATE if ow["state"] else 0) | (capi.POSE_PRIOR_GRAD_OVERWRITE_PRIOR if ow["prior"] else 0)
+    capi.check(capi.lib().banet_pose_prior_add_grad_f32(ctypes.byref(lv), ctypes.byref(pose_prior.c), capi.ptr(R), capi.ptr(T), capi.ptr(gAtA),
+                                                        capi.ptr(gAtb), ctypes.byref(out), capi.stream()))
+    return PosePriorGrad(**res)
+
+
+class _PosePriorApplyDiff(torch.autograd.Function):
+    """pose_prior_apply, out of place, with banet_pose_prior_add_grad_f32 as its backward; the prior's tensors enter as inputs so
+    that autograd sees them"""
+
+    @staticmethod
+    def forward(ctx, level, pose_prior, R, T, AtA, Atb, R0, T0, Lambda):
+        A2, b2 = AtA.clone(), Atb.clone()
+        pose_prior_apply(level, pose_prior, R, T, A2, b2)
+        ctx.level, ctx.pose_prior = level, pose_prior
+        ctx.shapes = [t.shape for t in (R, T, R0, T0, Lambda)]
+        ctx.save_for_backward(R, T)
+        ctx.set_materialize_grads(False)
+        return A2, b2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gA, gb):
+        if gA is None and gb is None:
+            return (None,) * 9
+        level = ctx.level
+        R, T = ctx.saved_tensors
+        B, K = level.B, level.K
+        P = 6 * max(level.pairs, 1) + K
+        dev = R.device
+        gA = torch.zeros(B, P, P, device=dev) if gA is None else capi.f32c(gA)
+        gb = torch.zeros(B, P, device=dev) if gb is None else capi.f32c(gb)
+        need = ctx.needs_input_grad
+        want = tuple(n for n, k in zip(("gR", "gT", "gR0", "gT0", "gLambda"), need[2:4] + need[6:9]) if k)
+        g = pose_prior_add_grad(level, ctx.pose_prior, R, T, gA, gb, want=want) if want else PosePriorGrad(*([None] * 6))
+        sR, sT, sR0, sT0, sL = ctx.shapes
+        rs = lambda t, s: None if t is None else t.reshape(s)           # noqa: E731
+        return (None, None, rs(g.gR, sR), rs(g.gT, sT), gA if need[4] else None, gb if need[5] else None, rs(g.gR0, sR0), rs(g.gT0, sT0),
+                rs(g.gLambda, sL))
+
+
+def pose_prior_apply_diff(level, pose_prior, R, T, AtA, Atb):
+    """pose_prior_apply attached to the autograd graph, OUT of place -> (AtA', Atb'): the inputs are not modified.  Differentiable
+    with respect to AtA, Atb, R, T and the prior's R0, T0 and Lambda (R and R0 as nine free entries each); `scale` stays a float
+    here (its gradient exists at the wrapper level: pose_prior_add_grad's gscale).  The backward is one
+    banet_pose_prior_add_grad_f32 call that asks only for what some input needs.  Composes with
+    dense_train.assemble_differentiable and ba_marginals_diff.  The empty pose prior returns (AtA, Atb) themselves."""
+    if _pose_prior_is_empty(pose_prior):
+        return AtA, Atb
+    pose_prior.check(level.B, level.pairs)
+    return _PosePriorApplyDiff.apply(level, pose_prior, capi.f32c(R), capi.f32c(T), capi.f32c(AtA), capi.f32c(Atb), pose_prior.R0,
+                                     pose_prior.T0, pose_prior.Lambda)
+
+
 def lm_level(level, mlp, l2_base, max_iters, early_termination, state, ws=None, params=None, prior=None, pose_prior=None):
     """banet_lm_level_ex_f32: the whole LM loop of one pyramid level, enqueued without host sync.
     params: an `lm_params(...)` value (None = the reference's defaults, legacy/ba.py:5-9).

@@ -710,6 +710,48 @@ int banet_lm_solve_pose_prior_f32(const banet_schedule_t* s, const banet_prior_t
                                   const banet_pose_prior_t* pose_priors /* n_levels entries, or NULL */, banet_state_t* st,
                                   banet_stream_t stream);
 
+/* (5g) the backward of (5f): training through a solve that carries a pose prior.  With G = gAtA'[0:m, 0:m] (raw, not symmetrised; row
+ *     stride P) and g = gAtb'[0:m] the gradients with respect to the post-prior matrices of one iteration, r, Jr, Lambda and
+ *     s = scale the quantities of (5f) at that iteration's R, T:
+ *         gAtA = gAtA', gAtb = gAtb'                               (pass through to the dense adjoint, unchanged; not written)
+ *         y = Jr g     X = Lambda Jr     Xt = Lambda^T Jr     u = Lambda r
+ *         gLambda += s (Jr G Jr^T - y r^T)                         (Lambda differentiated as the full matrix the forward reads)
+ *         gscale  += <G, Jr^T Lambda Jr> - <g, Jr^T Lambda r>      (float64 on the float32 values, fixed order)
+ *         gr = -s Lambda^T y      gJr_i = s (X G^T + Xt G)[block i] - s u_i g_i^T       (the 6 x 6 diagonal blocks only)
+ *         (gR_i, gT_i, gR0_i, gT0_i) += (d(r_i, Jr_i) / d(R_i, T_i, R0_i, T0_i))^T (gr_i, gJr_i)
+ *     the last line being the derivative of the chain of (5f) as the forward evaluates it, R and R0 as nine free entries each (the
+ *     convention of the dense adjoint's dpose[:, 0:9]).  Every 0 / 0 of the chain is taken analytically: at R = R0, T = T0
+ *     exactly the gradients are finite and equal the limit.  The derivative's coefficients of J^-1 and Q are series in theta^2
+ *     over the whole supported range (|phi| <= 3.0), with their own orders; the branch of theta / sin theta is the forward's.
+ *   banet_pose_prior_add_grad_f32   one iteration's step: one launch, ba_pose_prior_grad_kernel, one workgroup of four waves per
+ *       window whatever the shape, no workspace, no atomics; r_i and Jr_i are recomputed with the forward's own function (its
+ *       bits); the pose outputs in forward mode, one lane per (pose, input entry) and output element.  Every output pointer of
+ *       banet_pose_prior_grad_t is optional (NULL: not wanted, and not computed where that saves work); a subset gives the bits of
+ *       the full call.  All outputs accumulate (read-modify-write) unless BANET_POSE_PRIOR_GRAD_OVERWRITE_STATE (gR / gT are
+ *       written) / BANET_POSE_PRIOR_GRAD_OVERWRITE_PRIOR (gR0 / gT0 / gLambda / gscale are written).  It reads lv->B, K, pairs
+ *       and variant only.  BANET_ERR_INVALID_ARG before any launch: a struct (5f) refuses, the empty pose prior (it has no
+ *       backward), an unknown flag bit, reserved_ != 0, NULL lv / pp / R / T / gAtA / gAtb / out, no output at all;
+ *       BANET_ERR_UNSUPPORTED: a level (5f) refuses.
+ *     Enqueue only: no allocation, no synchronisation, no global state, one stream, capturable.  Every output element is written
+ *     by exactly one lane; every summation order is a function of pairs alone: a window's bits are the same alone and in any
+ *     batch.  BANET_VERSION is unchanged by this addition: detect the entry by its symbol.                                      */
+#define BANET_POSE_PRIOR_GRAD_OVERWRITE_STATE 1 /* write gR / gT instead of accumulating */
+#define BANET_POSE_PRIOR_GRAD_OVERWRITE_PRIOR 2 /* write gR0 / gT0 / gLambda / gscale instead of accumulating */
+
+typedef struct banet_pose_prior_grad { /* each pointer or NULL */
+  float* gR;         /* [B,pairs,3,3] */
+  float* gT;         /* [B,pairs,3] */
+  float* gR0;        /* [B,pairs,3,3] */
+  float* gT0;        /* [B,pairs,3] */
+  float* gLambda;    /* [B,m,m] */
+  float* gscale;     /* [B] */
+  int32_t flags;     /* BANET_POSE_PRIOR_GRAD_OVERWRITE_* or 0 */
+  int32_t reserved_; /* 0 */
+} banet_pose_prior_grad_t;
+
+int banet_pose_prior_add_grad_f32(const banet_level_t* lv, const banet_pose_prior_t* pp, const float* R, const float* T,
+                                  const float* gAtA, const float* gAtb, const banet_pose_prior_grad_t* out, banet_stream_t stream);
+
 /* (6) per-level preparation -- the step immediately before the LM loop.
  *   banet_resample_f32   data [B,H,W,C], warp [B,N,2] (x,y) -> out [B,N,C]
  *       mode BANET_RESAMPLE_ZERO_PAD : tf.contrib.resampler.resampler as called at
